@@ -5,14 +5,18 @@ Workload (BASELINE.json configs[1]): N x 768 f32 vectors (default N = 1M), index
 GPU (batch-synchronous schedule, M=16, ef_construction=200, cosine), then one STEP = one
 10k-query batched kNN (k=10, ef=128) with queries, index and outputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 N > 1: queries are independent — every rank holds a replica of the index (same
 seed → identical graph) and searches its own 10k-query batch; no data-path collective;
 value = all ranks' queries / max-over-ranks time ("weak").
 
-Rank 0 prints ONE JSON line (metric/value/... + roofline + cpu_baseline).
+Rank 0 prints ONE JSON line (metric/value/... + recall + roofline of the timed launches).  A plain
+run sets up, warms up, times the steps and stops there; --full adds everything else the line can
+carry (ef sweep, one query per call, cpu_baseline and parity, wave-order leg, recall-target and
+graph-quality legs, the graph block).  --dump-outputs DIR writes rank 0's answers of the last timed
+step (neighbor_ids, distances, result_counts) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -428,7 +432,15 @@ def main():
     ap.add_argument("--mode", default="replica", choices=["replica", "sharded"],
                     help="N>1: replica = same index on every GPU, queries sharded (no collective); sharded = config 3: "
                          "rowid mod N shards, same queries everywhere, RCCL all-gather + merge of per-shard top-k")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed steps (ef sweep, one query per call, CPU baselines and parity, "
+                         "wave-order, recall-target and graph-quality legs, graph block); the options above tune those legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write rank 0's answers of the last timed step as DIR/neighbor_ids.npy (float64), "
+                         "DIR/distances.npy (float32) and DIR/result_counts.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     t_run0 = time.perf_counter()
     dataset_spec(args.dataset)
     spawn_ranks_if_needed(args.gpus, os.path.abspath(__file__), sys.argv[1:])
@@ -467,7 +479,7 @@ def main():
     sharded = args.mode == "sharded" and world > 1
     streamed = N > args.stream_above  # e.g. 10M x 768: 30.7 GB fits HBM (288 GB) but is not held on the host
     if streamed:
-        if world > 1 or not args.no_cpu_baseline or args.recall_target > 0 or args.quality_n > 0:
+        if world > 1 or (args.full and (not args.no_cpu_baseline or args.recall_target > 0 or args.quality_n > 0)):
             progress("large N: streamed build; CPU baselines, the recall-target leg and the graph-quality leg are skipped")
         args.no_cpu_baseline, args.recall_target, args.quality_n = True, 0.0, 0
         if world > 1:
@@ -585,9 +597,19 @@ def main():
     alg_bytes = n_dist * D * 4 + n_exp * (2 * M) * 4 + n_dist * 4
     achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
 
-    # ---- recall@k against exact brute force on the device ----
     out_ids = np.empty((NQ, K), np.int64)
     g.dev_download(out_ids, d_ids)
+    if args.dump_outputs and rank == 0:  # the last timed step's answers, before any later leg reuses the buffers
+        out_ds = np.empty((NQ, K), np.float32)
+        out_cnt = np.empty(NQ, np.int32)
+        g.dev_download(out_ds, d_ds)
+        g.dev_download(out_cnt, d_cnt)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("neighbor_ids", out_ids.astype(np.float64)), ("distances", out_ds),
+                        ("result_counts", out_cnt.astype(np.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+    # ---- recall@k against exact brute force on the device ----
     nrec = min(args.recall_queries, NQ)
     recall = None
     if sharded:
@@ -602,6 +624,8 @@ def main():
     sweep = []
     if args.ef_sweep == "auto":
         args.ef_sweep = "128,256,512" if world == 1 and not streamed else ""
+    if not args.full:
+        args.ef_sweep = ""
     for ef2 in [int(x) for x in args.ef_sweep.split(",") if x]:
         run_steps(1, ef2)
         g.sync()
@@ -616,7 +640,7 @@ def main():
     # ---- one query per call (the SQL surface's shape: mn_hnsw_search from host memory, answer back in host memory): the
     #      latency-bound kernel (k_beam_coop, queues in registers), not the throughput one ----
     lone = None
-    if rank == 0 and world == 1 and not sharded and not streamed:
+    if args.full and rank == 0 and world == 1 and not sharded and not streamed:
         nl = min(200, NQ)
         for i in range(20):
             g.search(Q[i], K, EF)
@@ -644,7 +668,7 @@ def main():
     parity = None
     build_cpu = None
     exact_at_size = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_queries > 0:  # N=1 only (contract)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_queries > 0:  # N=1 only (contract)
         from oracle import orc
 
         progress("cpu baseline: oracle, then the compiled reference, on the same graph")
@@ -744,24 +768,24 @@ def main():
     at_target = None
     quality = None
     wave_leg = None
-    if rank == 0 and world == 1 and not streamed and args.order == "sse" and not args.no_wave_leg and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not streamed and args.order == "sse" and not args.no_wave_leg and not args.no_cpu_baseline:
         progress("wave-order leg: same data, MN_ORDER_WAVE, id sets vs the compiled reference")
         g.close()
         g = None
         wave_leg = wave_order_leg(pkg, args, dev_ord, M, EFC, X, Q)
-    if rank == 0 and world == 1 and args.recall_target > 0 and args.dataset == "gaussian":
+    if args.full and rank == 0 and world == 1 and args.recall_target > 0 and args.dataset == "gaussian":
         if g is not None:
             g.close()  # make room: the second index is the same size
         g = None
         X = None
         at_target = recall_target_leg(pkg, args, dev_ord, order, M, EFC, args.recall_target,
                                       [d for d in args.target_datasets.split(",") if d])
-    if rank == 0 and world == 1 and args.quality_n > 0:
+    if args.full and rank == 0 and world == 1 and args.quality_n > 0:
         quality = graph_quality_leg(pkg, args, dev_ord, order, M, EFC, min(args.quality_n, N),
                                     [d for d in args.quality_datasets.split(",") if d], (128, 256))
 
     graph = None
-    if rank == 0 and world == 1 and not streamed and not args.no_graph_block and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not streamed and not args.no_graph_block and not args.no_cpu_baseline:
         if g is not None:
             g.close()
         g = None

@@ -660,7 +660,7 @@ def test_batched_build_graph_is_as_good_as_the_exact_one(gpu):
     """The batch-synchronous build is what the headline index is built with; its graph differs from the reference's
     one-at-a-time graph.  Same vectors, both schedules: recall@10 (vs exact ground truth, all queries) within 0.01 at
     each ef, on embedding-like data and on the isotropic worst case.  (12k vectors here to keep the suite short; bench.py
-    runs the same leg at 50k x 768 in every default run and profiles/r02_graph_quality_100k.json holds 100k x 768 on three sets.)"""
+    runs the same leg at 50k x 768 in every --full run and profiles/r02_graph_quality_100k.json holds 100k x 768 on three sets.)"""
     import argparse
 
     import bench
@@ -710,6 +710,60 @@ def test_bench_streamed_build_path(gpu):
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["config"]["n"] == 150000 and j["recall_queries"] == 500 and j["recall_at_10"] > 0.8
     assert j["build_roofline"]["batches"] > 10 and j["cpu_baseline"] is None
+
+
+def _bench(args, timeout=600):
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + args, capture_output=True, text=True,
+                       timeout=timeout)
+    assert r.returncode == 0, r.stderr[-1500:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain run is set-up, warm-up, the timed steps and the line; --dump-outputs writes the last timed step's answers, and
+    the same arguments give the same inputs, hence the same answers, in another process."""
+    size = ["--num-vectors", "20000", "--dim", "64", "--nq", "500", "--steps", "3", "--warmup", "1"]
+    runs = [_bench(size + ["--dump-outputs", str(tmp_path / t)]) for t in ("a", "b")]
+    for j in runs:
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["unit"] == "queries/s"
+        assert abs(j["value"] - 500 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+        assert j["recall_at_10"] is not None and j["roofline"]["kernel_ms"] > 0
+        for leg in ("cpu_baseline", "parity_vs_oracle", "one_query_per_call", "wave_order", "at_recall_target",
+                    "graph_quality_exact_vs_batched", "graph"):
+            assert j[leg] is None, leg
+        assert j["ef_sweep"] == []
+    out = {}
+    for t in ("a", "b"):
+        out[t] = {n: np.load(tmp_path / t / f"{n}.npy") for n in ("neighbor_ids", "distances", "result_counts")}
+    a = out["a"]
+    assert a["neighbor_ids"].dtype == np.float64 and a["neighbor_ids"].shape == (500, 10)
+    assert a["distances"].dtype == np.float32 and a["distances"].shape == (500, 10)
+    assert a["result_counts"].dtype == np.float64 and (a["result_counts"] == 10).all()
+    assert ((a["neighbor_ids"] >= 1) & (a["neighbor_ids"] <= 20000)).all()
+    for n in a:
+        assert same_bits(a[n], out["b"][n]), n
+
+
+def test_bench_full_runs_the_other_legs(gpu, orc):
+    """--full: everything beyond the headline (ef sweep, one query per call, CPU baseline and parity, wave-order, recall-target
+    and graph-quality legs) at a size that takes seconds; the graph block has fixed sizes and is left out here."""
+    j = _bench(["--full", "--num-vectors", "3000", "--dim", "32", "--nq", "200", "--steps", "2", "--warmup", "1",
+                "--no-graph-block", "--quality-n", "1000", "--cpu-queries", "100", "--ref-queries", "50", "--exact-inserts", "50",
+                "--target-datasets", "lowrank16"])
+    assert j["steps"] == 2 and j["value"] > 0
+    assert j["parity_vs_oracle"]["ids_identical"] and j["cpu_baseline"]["value"] > 0
+    assert [r["ef"] for r in j["ef_sweep"]] == [128, 256, 512]
+    assert j["one_query_per_call"]["queries"] == 200
+    assert j["wave_order"] is not None and j["at_recall_target"]["datasets"][0]["dataset"] == "lowrank16"
+    assert j["graph_quality_exact_vs_batched"][0]["n"] == 1000 and j["graph"] is None
 
 
 def _bits(x):
