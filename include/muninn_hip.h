@@ -203,6 +203,8 @@ typedef struct {
     int64_t last_n_dist;     /* distance evaluations performed by that launch (device counter) */
     int64_t last_n_expanded; /* neighbour rows read by that launch */
     int64_t last_n_overflow; /* queries whose heaps exceeded workspace (must be 0) */
+    int64_t last_n_exact_rows; /* f32 rows read for those distances: last_n_dist minus the candidates the fp16 shadow's bound
+                                * rejected (MN_LOWPREC_FILTER; equal to last_n_dist with the filter off) */
 } mn_launch_stats;
 int mn_hnsw_last_launch(mn_index *idx, mn_launch_stats *out);
 /* Totals over the batch-synchronous inserts (MN_BUILD_BATCHED / mn_hnsw_build) since the last reset: HIP-event time of

@@ -170,6 +170,10 @@ struct WaveCtx {
     int rcap = 0, nr = 0;
     CoopCtx *coop = nullptr;
     int no_spec_rows = 0; // MN_SPEC_ROWS=0 (host): the helpers' rows are requested only once the visited probe has answered (A/B runs)
+    // beam_layer<LP>: the fp16 shadow's bound rejects candidates before their f32 rows are read (lp_on: this query may)
+    int lp_on = 0;
+    LoQuery lq = {0.0f, 0.0};
+    unsigned long long n_skip = 0; // distances decided by the bound alone (counted in n_dist as well)
 };
 DEVI bool getenv_spec_off(const WaveCtx &w) { return (w.no_spec_rows & 1) != 0; }
 
@@ -357,7 +361,11 @@ DEVI int greedy_layer(const MnDevIndex &ix, WaveCtx &w, int entry, int level, in
 }
 
 // src/hnsw_algo.c:347-448.  Results are left in the result heap; the caller drains it.
-template <int ORDER, int NCH, bool COH = false, bool WIDE = false, bool LOG = false>
+// LP (k_beam, search): once the results are full, a row's new candidates are first held against the worst result on a lower
+// bound from the fp16 shadow (lo_rows_bound); only those it cannot reject have their f32 rows read.  A rejected candidate has
+// d ≥ worst0 ≥ the worst at any later moment of the row, so the reference would not have pushed it either (see the pre-filter
+// below): same pushes in the same order, same counters.
+template <int ORDER, int NCH, bool COH = false, bool WIDE = false, bool LOG = false, bool LP = false>
 DEVI void beam_layer(const MnDevIndex &ix, WaveCtx &w, WHeap &cand, WHeap &res, unsigned *bitmap, int entry, int level,
                      int ef, int lane) {
     cand.size = 0;
@@ -420,8 +428,27 @@ DEVI void beam_layer(const MnDevIndex &ix, WaveCtx &w, WHeap &cand, WHeap &res, 
                 w.scratch[rank] = nb;
             __builtin_amdgcn_wave_barrier();
             int myslot = lane < n ? w.scratch[lane] : 0;
-            float d = ctx_distance<ORDER, NCH>(ix, w, myslot, n, lane);
             w.n_dist += n;
+            int ne = n; // candidates whose exact distance is computed: lanes < ne, in list order
+            if (LP && w.lp_on && res.size >= ef) {
+                const float worst0 = -u2f(rflu(hget(res, 1).x));
+                const float lb = lo_rows_bound(ix, w.q, w.lq, myslot, n, lane);
+                const bool keep = lane < n && !(lb >= worst0);
+                const unsigned long long km = __ballot(keep);
+                ne = __popcll(km);
+                if (ne < n) {
+                    w.n_skip += n - ne;
+                    const int kr = __popcll(km & ((1ull << lane) - 1ull));
+                    __builtin_amdgcn_wave_barrier();
+                    if (keep)
+                        w.scratch[kr] = myslot;
+                    __builtin_amdgcn_wave_barrier();
+                    myslot = lane < ne ? w.scratch[lane] : 0;
+                }
+            }
+            float d = 0.0f;
+            if (!LP || ne > 0)
+                d = ctx_distance<ORDER, NCH>(ix, w, myslot, ne, lane);
             PH_ADD(w, 2);
             // :413-425, in list order.  Once the result set is full an element can only be accepted
             // if it beats the worst AT THAT MOMENT, which never exceeds the worst now: pre-filter.
@@ -429,10 +456,10 @@ DEVI void beam_layer(const MnDevIndex &ix, WaveCtx &w, WHeap &cand, WHeap &res, 
             float worst_log = __builtin_inff();
             if (res.size >= ef) {
                 float worst0 = -u2f(rflu(hget(res, 1).x));
-                am = __ballot(lane < n && d < worst0);
+                am = __ballot(lane < ne && d < worst0);
                 worst_log = worst0;
             } else {
-                am = __ballot(lane < n);
+                am = __ballot(lane < ne);
             }
             if (LOG && !WIDE && w.rlog) // (speculative windows: what this row's expansion depended on, by list position)
                 log_row_detail(w, worst_log, __ballot(todo && ((am >> rank) & 1ull)), lane, 2);

@@ -11,11 +11,28 @@
 //   M_max — the reference grows lists without bound there — at which point the host re-strides the table.
 //   up_off   [cap]       int32 first pool row of the node, -1 when level == 0
 //   levels   [cap] int8, deleted [cap] u8, ids [cap] int64, dirty [cap] u8 (nodes to re-persist)
+//   vec_lo   [cap][ld]   fp16 shadow of vectors (row x = lo_meta.scale * vec_lo), only when mn_lo_enabled(ld)
+//   lo_meta  [cap]       MnLoMeta per row: scale, r_x = |x - x~|, bounds on |x|
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define MN_WAVE 64
+
+// ───────── low-precision shadow of the vectors (the one definition of its format: DESIGN.md §2, §3.1) ─────────
+// Row x of the index has a 2-byte copy h (IEEE fp16) and a power-of-two scale s; the dequantised row is x~_i = fl32(f32(h_i) * s),
+// computed the same way where the shadow is written (k_prep_rows) and where it is read (lo_rows_bound).  The search uses it only
+// to REJECT candidates on a certified lower bound of the exact distance (mn_beam.hpp beam_layer<LP>): results are unchanged.
+typedef unsigned short mn_lo_t; // fp16 bits
+struct __align__(16) MnLoMeta {
+    float scale; // s = 2^e
+    float resid; // r_x >= |x - x~| (rounded up); +inf: never filter this row (non-finite element, or |x| out of range)
+    float xn_lo; // cosine: sqrt(nb) rounded down, nb = the row's f32 norm (norms[]) the exact distance divides by; else |x| rounded down
+    float xn_hi; // |x| rounded up
+};
+// rows shorter than this read faster in f32 than the extra pass costs; rows must be whole 128-byte lines of fp16
+#define MN_LO_MIN_LD 192
+__host__ __device__ inline bool mn_lo_enabled(int ld) { return ld >= MN_LO_MIN_LD && (ld & 63) == 0; }
 constexpr int MN_ORDER_SSE_V = 0;  // muninn_hip.h mn_order
 constexpr int MN_ORDER_WAVE_V = 1;
 
@@ -36,6 +53,8 @@ struct MnDevIndex {
     int n_slots;
     int n_pool_rows;
     int has_deleted; // 0: no soft-deleted node exists — the per-candidate deleted[] gather of the searches is skipped
+    const mn_lo_t *vec_lo;   // [cap][ld] or null (see MnLoMeta)
+    const MnLoMeta *lo_meta; // [cap] or null
 };
 
 // One launch of the beam-search kernel (search or build flavour).
@@ -65,7 +84,7 @@ struct MnSearchArgs {
     int cand_gcap;
     uint2 *res_ovf;          // [nq][res_gcap]
     int res_gcap;
-    unsigned long long *counters; // [0] n_dist [1] n_expanded [2] overflowed queries
+    unsigned long long *counters; // [0] n_dist [1] n_expanded [2] overflowed queries [3] distances decided by the fp16 bound alone
     unsigned long long *q_counters; // or, when not null: [nq][4] the same per query, plain stores (a few queries answered into the
                                     // index's pinned host block: no counter memset before the launch, no copy after it)
     int use_tile;                 // SSE order: stage candidate rows through the LDS tile (coalesced loads)
@@ -99,7 +118,9 @@ void mn_module_touch_kernels();
 void mn_module_touch_seq();
 void mn_module_touch_spec();
 void mn_module_touch_build();
-void mn_launch_norms(const MnDevIndex &ix, int first_slot, int n, float *norms_out, hipStream_t st);
+// rows [first_slot, first_slot + n): |v|² (cosine, into norms_out) and, when ix.vec_lo is set, the fp16 shadow — one launch
+void mn_launch_prep_rows(const MnDevIndex &ix, int first_slot, int n, float *norms_out, mn_lo_t *lo_out, MnLoMeta *meta_out,
+                         hipStream_t st);
 void mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,
                           float *d_out, hipStream_t st);
 size_t mn_search_lds_bytes(int ld, bool tile);

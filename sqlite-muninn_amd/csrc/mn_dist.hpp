@@ -562,6 +562,126 @@ DEVI float rows_distance(const MnDevIndex &ix, const float *q_lds, float qnorm, 
     return cosine_finish(dot, qnorm, nb);
 }
 
+// ───────────────────────── the fp16 shadow: a certified lower bound on the exact distance ─────────────────────────
+// DESIGN.md §3.1 derives every factor below.  The approximate pass may sum in any order: the bound covers any order.
+
+// x~_i: the dequantised element, computed the same way by k_prep_rows (which derives r_x from it) and by the approximate pass
+DEVI float lo_deq(unsigned h, float s) { return __fmul_rn((float)__builtin_bit_cast(_Float16, (unsigned short)h), s); }
+DEVI double mn_gamma(int n) { // γ_n = n u / (1 - n u), u = 2^-24
+    const double nu = (double)n * 0x1p-24;
+    return nu / (1.0 - nu);
+}
+
+// UB lines of the row in flight per lane (8 lanes per row, 16 B each: one 128-byte line per row per load instruction), then the
+// sums: Σ q·x~ or Σ (q - x~)², f32, fused multiply-adds
+template <bool L2, int UB>
+DEVI void lo_lines(const uint4 *__restrict__ row, const float *q, float s, int lines, int &k, float &acc) {
+    for (; k + UB <= lines; k += UB) {
+        uint4 v[UB];
+#pragma unroll
+        for (int u = 0; u < UB; u++)
+            v[u] = row[8 * (k + u)];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < UB; u++) {
+            const float4 qa = *reinterpret_cast<const float4 *>(q + 64 * (k + u));
+            const float4 qb = *reinterpret_cast<const float4 *>(q + 64 * (k + u) + 4);
+            const float qe[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+            const unsigned w4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const float x = lo_deq((e & 1) ? (w4[e >> 1] >> 16) : (w4[e >> 1] & 0xffffu), s);
+                if (L2) {
+                    const float d = __fsub_rn(qe[e], x);
+                    acc = fmaf(d, d, acc);
+                } else {
+                    acc = fmaf(qe[e], x, acc);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0); // (q's LDS reads of the next line wait: 8 floats live, not 8 per line in flight)
+        }
+    }
+}
+
+// Approximate accumulations of n shadow rows (slot per lane, lanes < n valid) against q_lds; lane i < n gets row i's.  8 rows
+// per pass, lane (r, c) reads bytes 16c .. 16c+15 of every 128-byte line of row r.  `sc`: lane i < n holds row i's scale.
+template <bool L2>
+DEVI float lo_rows_accumulate(const MnDevIndex &ix, const float *q_lds, int myslot, float sc, int n, int lane) {
+    float mine = 0.0f;
+    // (an opaque copy of the lane id: what is derived from it is computed here, per call — hoisted out of the search loop, a
+    //  dozen such values would stay live through the exact distance walk and cost the kernel its occupancy)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int c = ln & 7, r = ln >> 3;
+    const int lines = ix.ld >> 6;
+    for (int t = 0; t < n; t += 8) {
+        const int rr = t + r < n ? t + r : n - 1;
+        const int sl = __shfl(myslot, rr);
+        const float s = __shfl(sc, rr);
+        const uint4 *row = reinterpret_cast<const uint4 *>(ix.vec_lo + (size_t)sl * ix.ld) + c;
+        const float *q = q_lds + 8 * c;
+        float acc = 0.0f;
+        int k = 0;
+        lo_lines<L2, 12>(row, q, s, lines, k, acc);
+        lo_lines<L2, 4>(row, q, s, lines, k, acc);
+        lo_lines<L2, 1>(row, q, s, lines, k, acc);
+        acc += quad_xor1(acc);
+        acc += quad_xor2(acc);
+        acc += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(acc), 0x101F)); // lanes xor 4
+        const float got = __shfl(acc, ((ln - t) & 7) << 3);
+        if (ln >= t && ln < t + 8)
+            mine = got;
+    }
+    return mine;
+}
+
+// Per query: what the bound needs of q.  qsq = fl(Σ q²) as the index's order computes it (for cosine: the very value the exact
+// distance divides by).  qn_hi ≥ |q|; not finite → the query never filters.
+struct LoQuery {
+    double qs_lo; // ≤ sqrt(qsq)
+    double qn_hi;
+};
+DEVI LoQuery lo_query(float qsq, int ld) {
+    LoQuery lq;
+    lq.qs_lo = sqrt((double)qsq) * (1.0 - 0x1p-40);
+    // qsq ≥ |q|² (1 - γ) minus what squares below the f32 range lost
+    const double lost = (double)ld * 0x1p-149;
+    lq.qn_hi = sqrt(((double)qsq + lost) / (1.0 - 2.0 * mn_gamma(ld + 8))) * (1.0 + 0x1p-40);
+    return lq;
+}
+
+// lane i < n: a lower bound on the exact distance of row i (slot myslot) — the distance rows_distance returns, bit for bit, is
+// never below it — or -inf where nothing can be certified.  A = the approximate accumulation, m = the row's MnLoMeta.
+DEVI float lo_lower_bound(int metric, float A, const MnLoMeta &m, const LoQuery &lq, int ld) {
+    const double a = A, r = m.resid, g = mn_gamma(ld + 8), u = 0x1p-24;
+    if (!(fabs(a) <= 3.0e38) || !(r <= 3.0e38))
+        return -__builtin_inff();
+    double lb;
+    if (metric == 0) {
+        // |q - x~| ≥ sqrt((A - underflow) (1 - γ')), |q - x| ≥ |q - x~| - r_x, d ≥ |q - x|² (1 - γ'): every error term doubled
+        // (the square root in f32: correctly rounded, and the f32 argument is within 2^-24 of the f64 one — 2^-21 covers both)
+        const double l = (double)sqrtf((float)(fmax(a - (double)ld * 0x1p-147, 0.0) * (1.0 - 4.0 * g))) * (1.0 - 0x1p-21) - 2.0 * r;
+        lb = l > 0.0 ? l * l * (1.0 - 4.0 * g) : 0.0;
+    } else {
+        // |dot_ref - A| ≤ |q| r_x + γ |q| (|x| + |x~|) (+ what underflow loses), doubled
+        const double e = 2.0 * (lq.qn_hi * (r + g * (2.0 * (double)m.xn_hi + r)) + (double)ld * 0x1p-147);
+        if (metric == 2) {
+            lb = -(a + e);
+        } else {
+            // the f32 denominator fl(fl(sqrt(qsq)) fl(sqrt(nb))) is at least den: qsq and nb are the very f32 values the exact
+            // distance uses (xn_lo ≤ sqrt(nb) was taken from the row's stored norm, so no bound on how nb was summed is needed —
+            // rows whose squares underflow included); below the reference's 1e-30 guard: no bound
+            const double den = lq.qs_lo * (double)m.xn_lo * (1.0 - 8.0 * u);
+            if (!(den >= 1e-28))
+                return -__builtin_inff();
+            lb = 1.0 - fmax(a + e, 0.0) / den * (1.0 + 4.0 * u);
+        }
+    }
+    lb -= fabs(lb) * 0x1p-20 + 0x1p-120; // the reference's last rounding, and this arithmetic's own
+    const float f = __double2float_rd(lb);
+    return f == f ? f : -__builtin_inff();
+}
+
 // |v|² of the vector in LDS, in the index's order
 template <int ORDER>
 DEVI float lds_self_norm(const float *q_lds, int dim, int ld, int lane) {
@@ -570,5 +690,15 @@ DEVI float lds_self_norm(const float *q_lds, int dim, int ld, int lane) {
         return __shfl(v, 0);
     }
     return wave_row_generic<false>(q_lds, q_lds, ld, lane);
+}
+
+// lane i < n: the bound of row i (myslot), from the shadow; lanes ≥ n: -inf
+DEVI float lo_rows_bound(const MnDevIndex &ix, const float *q_lds, const LoQuery &lq, int myslot, int n, int lane) {
+    MnLoMeta m = {1.0f, __builtin_inff(), 0.0f, 0.0f};
+    if (lane < n)
+        m = ix.lo_meta[myslot];
+    const float A = ix.metric == 0 ? lo_rows_accumulate<true>(ix, q_lds, myslot, m.scale, n, lane)
+                                   : lo_rows_accumulate<false>(ix, q_lds, myslot, m.scale, n, lane);
+    return lane < n ? lo_lower_bound(ix.metric, A, m, lq, ix.ld) : -__builtin_inff();
 }
 

@@ -129,6 +129,8 @@ struct mn_index {
     int ht_cap = 256;
     // device state
     DevBuf<float> d_vectors, d_norms;
+    DevBuf<mn_lo_t> d_vec_lo;    // fp16 shadow of d_vectors, grown with it (mn_lo_enabled(ld) only; mn_device.hpp MnLoMeta)
+    DevBuf<MnLoMeta> d_lo_meta;
     DevBuf<int> d_links0, d_links_up, d_up_off;
     DevBuf<signed char> d_levels;
     DevBuf<unsigned char> d_deleted, d_dirty;
@@ -178,7 +180,7 @@ struct mn_index {
     DevBuf<float> sh_gd, sh_ld;
     long long last_spec_searched = 0; // searches the last speculative build ran (≥ nodes inserted)
     bool broken = false; // an insert failed after its kernels had begun to rewrite link rows: nothing can be trusted
-    mn_launch_stats last = {0, 0, 0, 0};
+    mn_launch_stats last = {0, 0, 0, 0, 0};
 };
 
 // ───────────────────────── small host helpers ─────────────────────────
@@ -343,6 +345,8 @@ static MnDevIndex dev_view(mn_index *x) {
     v.n_slots = x->n_slots;
     v.n_pool_rows = x->n_pool_rows;
     v.has_deleted = x->n_deleted > 0;
+    v.vec_lo = x->d_vec_lo.p;
+    v.lo_meta = x->d_lo_meta.p;
     return v;
 }
 
@@ -413,6 +417,10 @@ static int sync_meta(mn_index *x) {
     size_t hs = std::max(ns, (size_t)x->slot_hint); // a bulk build has announced its final slot count
     if (x->d_vectors.reserve(ns * x->ld, true, st, -1, hs * x->ld)) return -1;
     if (x->d_norms.reserve(ns, true, st, -1, hs)) return -1;
+    if (mn_lo_enabled(x->ld)) {
+        if (x->d_vec_lo.reserve(ns * x->ld, true, st, -1, hs * x->ld)) return -1;
+        if (x->d_lo_meta.reserve(ns, true, st, -1, hs)) return -1;
+    }
     if (x->d_links0.reserve(ns * x->W0, true, st, 0xFF, hs * x->W0)) return -1;
     if (x->d_links_up.reserve((size_t)std::max(1, x->n_pool_rows) * x->WU, true, st, 0xFF)) return -1;
     if (x->d_up_off.reserve(ns, true, st, -1, hs)) return -1;
@@ -453,6 +461,12 @@ static int sync_meta(mn_index *x) {
     return 0;
 }
 
+// what is derived from rows [first, first + n) once they are in place: norms (cosine) and the fp16 shadow, one launch
+static void prep_rows(mn_index *x, int first, int n) {
+    mn_launch_prep_rows(dev_view(x), first, n, x->metric == MN_METRIC_COSINE ? x->d_norms.p : nullptr, x->d_vec_lo.p,
+                        x->d_lo_meta.p, x->stream);
+}
+
 static int upload_vectors(mn_index *x, int first, const float *vecs, int n, bool src_on_device) {
     hipStream_t st = x->stream;
     // (src_on_device: the rows are already in HBM — mn_hnsw_build_dev — and never visit the host)
@@ -463,8 +477,7 @@ static int upload_vectors(mn_index *x, int first, const float *vecs, int n, bool
         for (int i = x->dim; i < x->ld; i++)
             pv[i] = 0.0f;
         HIPCHK(hipMemcpyAsync(x->d_vectors.p + (size_t)first * x->ld, pv, (size_t)x->ld * sizeof(float), hipMemcpyHostToDevice, st));
-        if (x->metric == MN_METRIC_COSINE)
-            mn_launch_norms(dev_view(x), first, 1, x->d_norms.p, st);
+        prep_rows(x, first, 1);
         return 0; // the insert's own synchronisation covers the copy
     }
     if (x->ld == x->dim) {
@@ -474,8 +487,7 @@ static int upload_vectors(mn_index *x, int first, const float *vecs, int n, bool
         HIPCHK(hipMemcpy2DAsync(x->d_vectors.p + (size_t)first * x->ld, (size_t)x->ld * sizeof(float), vecs,
                                 (size_t)x->dim * sizeof(float), (size_t)x->dim * sizeof(float), (size_t)n, kind, st));
     }
-    if (x->metric == MN_METRIC_COSINE)
-        mn_launch_norms(dev_view(x), first, n, x->d_norms.p, st);
+    prep_rows(x, first, n);
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
@@ -686,6 +698,7 @@ extern "C" void mn_hnsw_destroy(mn_index *x) {
     if (x->stream)
         (void)hipStreamSynchronize(x->stream);
     x->d_vectors.release(); x->d_norms.release(); x->d_links0.release(); x->d_links_up.release();
+    x->d_vec_lo.release(); x->d_lo_meta.release();
     x->d_up_off.release(); x->d_levels.release(); x->d_deleted.release(); x->d_dirty.release(); x->d_ids.release();
     x->ws_bm0.release(); x->ws_bmu.release(); x->ws_cand.release(); x->ws_res.release(); x->ws_q.release();
     x->ws_outd.release(); x->ws_outi.release(); x->ws_outc.release(); x->ws_qslots.release(); x->ws_sel.release();
@@ -785,6 +798,7 @@ static int fetch_counters(mn_index *x) {
     x->last.last_n_dist = (int64_t)c[0];
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
+    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
     return 0;
 }
 
@@ -900,6 +914,7 @@ static int counters_from(mn_index *x, const unsigned long long *c) {
     x->last.last_n_dist = (int64_t)c[0];
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
+    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
     return 0;
 }
 
@@ -934,6 +949,9 @@ static int search_small(mn_index *x, const float *queries, int64_t nq, int k, in
         for (int64_t q = 0; q < nq; q++)
             for (int i = 0; i < 3; i++)
                 tot[i] += qc[q * 4 + i];
+        for (int64_t q = 0; q < nq; q++)
+            tot[3] += qc[q * 4 + 3];
+        x->last.last_n_exact_rows = (int64_t)(tot[0] - tot[3]);
         x->last.last_n_dist = (int64_t)tot[0];
         x->last.last_n_expanded = (int64_t)tot[1];
         x->last.last_n_overflow = (int64_t)tot[2];

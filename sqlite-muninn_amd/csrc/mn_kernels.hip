@@ -1,6 +1,6 @@
 // mn_kernels.hip — hand-written gfx950 kernels for sqlite-muninn's HNSW hot path.
 //
-//   k_norms        |v|² per row in the index's summation order (cosine)
+//   k_prep_rows    |v|² per row in the index's summation order (cosine) and the fp16 shadow of the row
 //   k_dist_batch   vec_*_distance(query, rows[i])                       src/vec_math.c:78-143
 //   k_beam         greedy descent + ef-bounded beam search, one 64-lane wavefront per query
 //                  (search flavour: hnsw_search src/hnsw_algo.c:670-704; build flavour: the search
@@ -25,10 +25,20 @@
 
 #include "mn_dist.hpp"
 
-// ───────────────────────── k_norms ─────────────────────────
+// ───────────────────────── k_prep_rows ─────────────────────────
+// Everything derived from a row when it is written (upload_vectors): |v|² in the index's order (cosine) and the fp16 shadow
+// (MnLoMeta, mn_device.hpp).  One wavefront per row, one launch per upload — a one-row INSERT gets no extra launch.
+
+DEVI double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        v += __shfl_xor(v, m);
+    return v;
+}
 
 template <int ORDER>
-__global__ void __launch_bounds__(64) k_norms(MnDevIndex ix, int first_slot, int n, float *norms_out) {
+__global__ void __launch_bounds__(64)
+    k_prep_rows(MnDevIndex ix, int first_slot, int n, float *norms_out, mn_lo_t *lo_out, MnLoMeta *meta_out) {
     extern __shared__ float lds[];
     const int lane = threadIdx.x;
     int slot = first_slot + blockIdx.x;
@@ -39,19 +49,67 @@ __global__ void __launch_bounds__(64) k_norms(MnDevIndex ix, int first_slot, int
         lds[i] = row[i];
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    float v = lds_self_norm<ORDER>(lds, ix.dim, ix.ld, lane);
-    if (lane == 0)
-        norms_out[slot] = v;
+    float nbv = 0.0f; // (cosine) the row's norm as the exact distance will read it
+    if (norms_out) {
+        nbv = lds_self_norm<ORDER>(lds, ix.dim, ix.ld, lane);
+        if (lane == 0)
+            norms_out[slot] = nbv;
+    }
+    if (!lo_out)
+        return;
+    // scale 2^e: the largest element lands in [2^14, 2^15) of fp16 (max 65504)
+    float mx = 0.0f;
+    bool bad = false;
+    for (int i = lane; i < ix.ld; i += 64) {
+        const float v = lds[i];
+        bad |= !(fabsf(v) <= 3.4028235e38f);
+        mx = fmaxf(mx, fabsf(v));
+    }
+    for (int m = 32; m >= 1; m >>= 1)
+        mx = fmaxf(mx, __shfl_xor(mx, m));
+    bad = __ballot(bad) != 0;
+    int e = 0;
+    if (!bad && mx > 0.0f) {
+        e = ilogbf(mx) - 14;
+        e = e < -140 ? -140 : (e > 127 ? 127 : e);
+    }
+    const float s = ldexpf(1.0f, e);
+    double r2 = 0.0, x2 = 0.0;
+    mn_lo_t *lo = lo_out + (size_t)slot * ix.ld;
+    for (int i = lane; i < ix.ld; i += 64) {
+        const float v = lds[i];
+        const _Float16 h = bad ? (_Float16)0.0f : (_Float16)ldexpf(v, -e);
+        const unsigned short hb = __builtin_bit_cast(unsigned short, h);
+        lo[i] = hb;
+        const double dv = (double)v - (double)lo_deq(hb, s); // exact: both are f32 values, and x~ ≈ x
+        r2 += dv * dv;
+        x2 += (double)v * (double)v;
+    }
+    r2 = wave_sum_f64(r2);
+    x2 = wave_sum_f64(x2);
+    if (lane == 0) {
+        MnLoMeta m;
+        m.scale = s;
+        // f64 sums of at most a few thousand terms: relative error far below the 2^-36 taken off / added here
+        const double xn = sqrt(x2), rx = sqrt(r2);
+        m.xn_lo = norms_out ? __double2float_rd(sqrt((double)nbv) * (1.0 - 0x1p-40)) : __double2float_rd(xn * (1.0 - 0x1p-36));
+        m.xn_hi = __double2float_ru(xn * (1.0 + 0x1p-36));
+        m.resid = __double2float_ru(rx * (1.0 + 0x1p-36) + 0x1p-140);
+        if (bad || !(m.xn_hi <= 3.0e38f) || !(m.resid <= 3.0e38f))
+            m.resid = __builtin_inff(); // never filtered
+        meta_out[slot] = m;
+    }
 }
 
-void mn_launch_norms(const MnDevIndex &ix, int first_slot, int n, float *norms_out, hipStream_t st) {
-    if (n <= 0)
+void mn_launch_prep_rows(const MnDevIndex &ix, int first_slot, int n, float *norms_out, mn_lo_t *lo_out, MnLoMeta *meta_out,
+                         hipStream_t st) {
+    if (n <= 0 || (!norms_out && !lo_out))
         return;
     size_t lds = (size_t)ix.ld * sizeof(float);
     if (ix.order == MN_ORDER_SSE_V)
-        hipLaunchKernelGGL(k_norms<MN_ORDER_SSE_V>, dim3(n), dim3(64), lds, st, ix, first_slot, n, norms_out);
+        hipLaunchKernelGGL(k_prep_rows<MN_ORDER_SSE_V>, dim3(n), dim3(64), lds, st, ix, first_slot, n, norms_out, lo_out, meta_out);
     else
-        hipLaunchKernelGGL(k_norms<MN_ORDER_WAVE_V>, dim3(n), dim3(64), lds, st, ix, first_slot, n, norms_out);
+        hipLaunchKernelGGL(k_prep_rows<MN_ORDER_WAVE_V>, dim3(n), dim3(64), lds, st, ix, first_slot, n, norms_out, lo_out, meta_out);
 }
 
 // ───────────────────────── k_dist_batch ─────────────────────────
@@ -148,7 +206,8 @@ void mn_launch_dist_batch(int metric, int order, const float *d_query, const flo
 
 // one query, one (leading) wavefront; `coop` = the group's shared area when helpers stand by (k_beam_coop)
 // LAT: a latency-bound launch (few queries, one workgroup each): the layer searches keep their queues in registers (beam_layer_auto)
-template <int ORDER, int NCH, bool BUILD, bool WIDE, bool LAT = false>
+// LP: the layer-0 search of a batch filters on the fp16 shadow first (beam_layer<LP>)
+template <int ORDER, int NCH, bool BUILD, bool WIDE, bool LAT = false, bool LP = false>
 DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long long qi, const int lane, unsigned char *smem,
                      CoopCtx *coop, unsigned *lds_bitmap = nullptr) {
     // LDS carve: cand heap | result heap | scratch | query
@@ -186,6 +245,10 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
         if (lane == 0)
             *coop->qnorm = w.qnorm;
     }
+    if (LP) {
+        w.lq = lo_query(ix.metric == 1 ? w.qnorm : lds_self_norm<ORDER>(q, ix.dim, ix.ld, lane), ix.ld);
+        w.lp_on = w.lq.qn_hi <= 1.0e300;
+    }
     if (BUILD && a.readlog) {
         w.rlog = a.readlog + (size_t)qi * a.readcap * MN_RLOG_INTS;
         w.rcap = a.readcap;
@@ -215,7 +278,7 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
         if (LAT)
             beam_layer_auto<ORDER, NCH, false, WIDE>(ix, w, cand, res, bm0, a.bm0_words, cur, 0, a.ef, lane);
         else
-            beam_layer<ORDER, NCH, false, WIDE>(ix, w, cand, res, bm0, cur, 0, a.ef, lane);
+            beam_layer<ORDER, NCH, false, WIDE, false, LP>(ix, w, cand, res, bm0, cur, 0, a.ef, lane);
         int count = res.size;
         int outn = count < a.k ? count : a.k;
         for (int i = count - 1; i >= 0; i--) { // :436-441
@@ -272,21 +335,24 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
             a.q_counters[(size_t)qi * 4 + 0] = w.n_dist;
             a.q_counters[(size_t)qi * 4 + 1] = w.n_exp;
             a.q_counters[(size_t)qi * 4 + 2] = (cand.ovf || res.ovf) ? 1ull : 0ull;
+            a.q_counters[(size_t)qi * 4 + 3] = w.n_skip;
         } else {
             atomicAdd(&a.counters[0], w.n_dist);
             atomicAdd(&a.counters[1], w.n_exp);
             if (cand.ovf || res.ovf)
                 atomicAdd(&a.counters[2], 1ull);
+            if (LP && w.n_skip)
+                atomicAdd(&a.counters[3], w.n_skip);
         }
     }
 }
 
-template <int ORDER, int NCH, bool BUILD, bool WIDE = false>
+template <int ORDER, int NCH, bool BUILD, bool WIDE = false, bool LP = false>
 __global__ void __launch_bounds__(64) k_beam(MnDevIndex ix, MnSearchArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     if ((long long)blockIdx.x >= a.nq)
         return;
-    beam_query<ORDER, NCH, BUILD, WIDE>(ix, a, blockIdx.x, threadIdx.x, smem, nullptr);
+    beam_query<ORDER, NCH, BUILD, WIDE, false, LP>(ix, a, blockIdx.x, threadIdx.x, smem, nullptr);
 }
 
 // Few queries (a single xFilter, a window of speculative inserts): one WORKGROUP per query, see CoopCtx (mn_beam.hpp).
@@ -426,6 +492,16 @@ static void launch_beam(const MnDevIndex &ix, const MnSearchArgs &a, bool build,
             launch_coop<ORDER, NCH, true, false>(ix, a, base, tot, st);
         else
             launch_coop<ORDER, NCH, false, false>(ix, a, base, tot, st);
+        return;
+    }
+    // a search over an index with the fp16 shadow: reject on its bound first (MN_LOWPREC_FILTER=0: never; read per launch, so
+    // that one process can A/B the two)
+    const char *lp = getenv("MN_LOWPREC_FILTER");
+    if (!build && ix.vec_lo && ix.lo_meta && !(lp && atoi(lp) == 0)) {
+        if (wide)
+            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, true, true>), grid, block, lds, st, ix, a);
+        else
+            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, false, true>), grid, block, lds, st, ix, a);
         return;
     }
     if (wide) {
