@@ -66,17 +66,22 @@ long long mn_debug_fault_alloc(long long nth);
 /* src/vec_math.c:192-204: "l2" | "cosine" | "inner_product" → 0, else -1 */
 int mn_vec_parse_metric(const char *name, int *out_metric);
 /* vec_get_distance_func(metric)(query, rows[i], dim) for i < n  (src/vec_math.c:78-143,180-190).
- * Host pointers; rows is [n][dim] row-major.  Returns 0 / -1. */
+ * Host pointers; rows is [n][dim] row-major.  Returns 0 / -1 (also when the query and a row, 8 * round_up(dim, 4) bytes, do not
+ * fit the LDS the device grants one workgroup: nothing is computed then). */
 int mn_vec_dist_batch(int metric, int order, const float *query, const float *rows, int64_t n, int dim, float *out);
 
 /* ---- hnsw_algo.c replacements (a5-a12) ---- */
 /* hnsw_create (src/hnsw_algo.c:181-208).  M_max0 = 2M, rng seed 42.  device = HIP ordinal.
  * 2 <= M <= 512 (the reference has no upper bound; here a list of 2M + 1 entries is pruned inside one workgroup's LDS;
- * rows of more than 64 links are walked 64 at a time); NULL + mn_last_error() otherwise, or when no gfx950 device is
+ * rows of more than 64 links are walked 64 at a time) and dim <= mn_hnsw_max_dim(M, device) (the reference has no bound either;
+ * here kernels stage rows in LDS); NULL + mn_last_error() otherwise, or when no gfx950 device is
  * available (there is no CPU fallback).  The first index a process creates on a device also has HIP load the library's kernels
  * there (tens of milliseconds, once), so that no later query or insert pays for it. */
 mn_index *mn_hnsw_create(int dim, int metric, int M, int ef_construction);
 mn_index *mn_hnsw_create_on(int dim, int metric, int M, int ef_construction, int device);
+/* The largest dim mn_hnsw_create_on accepts for this M on this device: every kernel an index launches must hold its rows in
+ * LDS (64 KB, or the device's opt-in limit where a kernel asks for it).  -1 on bad parameters. */
+int mn_hnsw_max_dim(int M, int device);
 /* hnsw_destroy (:210-220) */
 void mn_hnsw_destroy(mn_index *idx);
 /* hnsw_seed_rng (:222-224) */

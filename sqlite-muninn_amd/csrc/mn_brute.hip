@@ -103,11 +103,13 @@ static int pick_nch_bf(int ld) {
     return 0;
 }
 
+size_t mn_bruteforce_lds_bytes(int ld) { return (size_t)ld * sizeof(float) + 4 * BF_KMAX * (sizeof(float) + sizeof(int)); }
+
 void mn_launch_bruteforce(const MnDevIndex &ix, const float *d_queries, long long nq, int k, long long *d_out_ids,
                           float *, hipStream_t st) {
     if (nq <= 0 || k <= 0 || k > BF_KMAX)
         return;
-    size_t lds = (size_t)ix.ld * sizeof(float) + 4 * BF_KMAX * (sizeof(float) + sizeof(int));
+    size_t lds = mn_bruteforce_lds_bytes(ix.ld);
     dim3 grid((unsigned)nq), block(256);
 #define MN_BF(O, N) hipLaunchKernelGGL((k_bruteforce<O, N>), grid, block, lds, st, ix, d_queries, nq, k, d_out_ids)
     if (ix.order == MN_ORDER_SSE_V) {

@@ -390,13 +390,20 @@ static int pick_nch_b(int ld) {
     return 0;
 }
 
+static int reverse_lw(int WX) {
+    const int LW = (WX + 64 + 63) & ~63; // the row is staged 64 links at a time, then one more / a chunk of 64 sources is appended
+    return LW < 192 ? 192 : LW;
+}
+static int reverse_bm_words(int nq) { return ((nq + 31) / 32 + 3) & ~3; } // sources of one target by batch index
+size_t mn_link_reverse_lds_bytes(int ld, int WX, int nq) {
+    return (size_t)reverse_lw(WX) * 5 * sizeof(int) + (size_t)reverse_bm_words(nq) * sizeof(unsigned) + (size_t)ld * sizeof(float);
+}
+
 template <int ORDER, int NCH>
 static void launch_reverse(const MnDevIndex &ix, const MnLinkArgs &a, int max_tuples, hipStream_t st) {
-    int LW = (ix.WX + 64 + 63) & ~63; // the row is staged 64 links at a time, then one more / a chunk of 64 sources is appended
-    if (LW < 192)
-        LW = 192;
-    const int bm_words = ((a.nq + 31) / 32 + 3) & ~3; // sources of one target by batch index
-    size_t lds = (size_t)LW * 5 * sizeof(int) + (size_t)bm_words * sizeof(unsigned) + (size_t)ix.ld * sizeof(float);
+    const int LW = reverse_lw(ix.WX);
+    const int bm_words = reverse_bm_words(a.nq);
+    const size_t lds = mn_link_reverse_lds_bytes(ix.ld, ix.WX, a.nq);
     hipLaunchKernelGGL((k_link_reverse<ORDER, NCH>), dim3(max_tuples), dim3(64), lds, st, ix, a, LW, bm_words);
 }
 

@@ -121,9 +121,15 @@ void mn_module_touch_build();
 // rows [first_slot, first_slot + n): |v|² (cosine, into norms_out) and, when ix.vec_lo is set, the fp16 shadow — one launch
 void mn_launch_prep_rows(const MnDevIndex &ix, int first_slot, int n, float *norms_out, mn_lo_t *lo_out, MnLoMeta *meta_out,
                          hipStream_t st);
-void mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,
-                          float *d_out, hipStream_t st);
+int mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,
+                         float *d_out, hipStream_t st); // -1: the rows do not fit the LDS the device grants, or the launch failed
+size_t mn_dist_batch_lds_bytes(int ld);
 size_t mn_search_lds_bytes(int ld, bool tile);
+size_t mn_coop_lds_bytes(int ld, bool tile);                // k_beam_coop without distance tiles or visited bitmap
+size_t mn_spec_commit_min_lds_bytes(int ld);                // k_spec_commit with one wavefront
+size_t mn_link_reverse_lds_bytes(int ld, int WX, int nq);   // k_link_reverse for a batch of nq nodes
+size_t mn_bruteforce_lds_bytes(int ld);                     // k_bruteforce
+inline size_t mn_row_lds_bytes(int ld) { return (size_t)ld * sizeof(float); } // k_prep_rows, k_edge_rows: one staged row
 int mn_launch_search(const MnDevIndex &ix, const MnSearchArgs &a, bool build, hipStream_t st);
 void mn_launch_bruteforce(const MnDevIndex &ix, const float *d_queries, long long nq, int k, long long *d_out_ids,
                           float *d_scratch, hipStream_t st);

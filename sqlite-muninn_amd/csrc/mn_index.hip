@@ -632,13 +632,65 @@ extern "C" int mn_vec_dist_batch(int metric, int order, const float *query, cons
     HIPCHK(hipMemset(dr.p, 0, (size_t)n * ld * sizeof(float)));
     HIPCHK(hipMemcpy2D(dr.p, (size_t)ld * sizeof(float), rows, (size_t)dim * sizeof(float), (size_t)dim * sizeof(float),
                        (size_t)n, hipMemcpyHostToDevice));
-    mn_launch_dist_batch(metric, order, dq.p, dr.p, n, dim, ld, dout.p, nullptr);
+    if (mn_launch_dist_batch(metric, order, dq.p, dr.p, n, dim, ld, dout.p, nullptr)) {
+        set_err("mn_vec_dist_batch: dim=%d needs %zu bytes of LDS, this device grants %zu", dim, mn_dist_batch_lds_bytes(ld),
+                mn_lds_optin_limit());
+        return -1;
+    }
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 } MN_GUARD_END(set_err, MN_NOTHING, -1)
 
 // ───────────────────────── create / destroy ─────────────────────────
+
+// Whether an index of rows of ld floats and this M fits the LDS of every kernel it launches, by the launchers' own formulas: 64 KB
+// where a launcher never asks for more, what the device grants where it does (k_insert_seq).  The optional parts (distance tiles,
+// precomputed prunes, visited bitmaps) are added only where they fit and are left out.  The batched link step is taken at the
+// build's default batch of 8192 nodes (its bitmap grows with the batch, not with the row).
+static bool ld_fits(int ld, int M, size_t optin) {
+    const size_t lim = 64 * 1024;
+    MnDevIndex v;
+    memset(&v, 0, sizeof(v));
+    v.ld = ld;
+    v.M0 = v.W0 = 2 * M; // src/hnsw_algo.c:188
+    v.MU = v.WU = M;
+    v.WX = 2 * M;
+#ifdef MN_SSE_TILE_PATH
+    const bool tile = true;
+#else
+    const bool tile = false;
+#endif
+    return mn_search_lds_bytes(ld, tile) <= lim && mn_coop_lds_bytes(ld, tile) <= lim && // k_beam, k_beam_coop
+           mn_insert_seq_lds_bytes(v) <= optin &&                                          // k_insert_seq (asks for the grant)
+           (v.W0 > 64 || mn_spec_commit_min_lds_bytes(ld) <= lim) &&                     // k_spec_commit (M <= 32 only)
+           mn_link_reverse_lds_bytes(ld, v.WX, 8192) <= lim &&                            // k_link_reverse
+           mn_bruteforce_lds_bytes(ld) <= lim && mn_row_lds_bytes(ld) <= lim;             // k_bruteforce, k_prep_rows, k_edge_rows
+}
+// the largest dimension an index with this M can have on this device (every formula grows with ld); 0: none
+static int max_dim(int M, int device) {
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    if (cur != device)
+        (void)hipSetDevice(device);
+    const size_t optin = mn_lds_optin_limit();
+    if (cur != device)
+        (void)hipSetDevice(cur);
+    int lo = 0, hi = 1 << 20; // ld = 4 lo fits (or lo = 0), ld = 4 hi does not
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        (ld_fits(4 * mid, M, optin) ? lo : hi) = mid;
+    }
+    return 4 * lo;
+}
+extern "C" int mn_hnsw_max_dim(int M, int device) try {
+    int ndev = 0;
+    if (M < 2 || M > MN_MAX_M || hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        set_err("mn_hnsw_max_dim: bad parameters or no HIP device %d", device);
+        return -1;
+    }
+    return max_dim(M, device);
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
 
 extern "C" mn_index *mn_hnsw_create_on(int dim, int metric, int M, int ef_construction, int device) try {
     if (dim <= 0 || M < 2 || ef_construction < 1 || metric < 0 || metric > 2) {
@@ -652,6 +704,11 @@ extern "C" mn_index *mn_hnsw_create_on(int dim, int metric, int M, int ef_constr
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
         set_err("mn_hnsw_create: HIP device %d not available (no CPU fallback)", device);
+        return nullptr;
+    }
+    // the reference has no upper bound; here every kernel stages rows of the index in LDS
+    if (const int lim = max_dim(M, device); dim > lim) {
+        set_err("mn_hnsw_create: dim=%d exceeds this build's limit of %d for M=%d on device %d", dim, lim, M, device);
         return nullptr;
     }
     mn_index *x = new mn_index();

@@ -105,7 +105,7 @@ void mn_launch_prep_rows(const MnDevIndex &ix, int first_slot, int n, float *nor
                          hipStream_t st) {
     if (n <= 0 || (!norms_out && !lo_out))
         return;
-    size_t lds = (size_t)ix.ld * sizeof(float);
+    size_t lds = mn_row_lds_bytes(ix.ld);
     if (ix.order == MN_ORDER_SSE_V)
         hipLaunchKernelGGL(k_prep_rows<MN_ORDER_SSE_V>, dim3(n), dim3(64), lds, st, ix, first_slot, n, norms_out, lo_out, meta_out);
     else
@@ -180,24 +180,34 @@ static int pick_nch(int ld) {
     return 0;
 }
 
-void mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,
-                          float *d_out, hipStream_t st) {
+// the query and one staged row: past 64 KB (ld > 8192) the kernel asks for the opt-in; beyond what the device grants, -1 and
+// nothing launched
+size_t mn_dist_batch_lds_bytes(int ld) { return (size_t)ld * sizeof(float) * 2; }
+
+template <int ORDER, int NCH>
+static int launch_dist_batch(int metric, const float *d_query, const float *d_rows, long long n, int dim, int ld, float *d_out,
+                             hipStream_t st) {
+    const size_t lds = mn_dist_batch_lds_bytes(ld);
+    if (lds > mn_lds_optin_limit() || !mn_lds_grant(reinterpret_cast<const void *>(k_dist_batch<ORDER, NCH>), lds))
+        return -1;
+    hipLaunchKernelGGL((k_dist_batch<ORDER, NCH>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, metric, d_query, d_rows, n,
+                       dim, ld, d_out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,
+                         float *d_out, hipStream_t st) {
     if (n <= 0)
-        return;
-    dim3 grid((unsigned)((n + 63) / 64)), block(64);
-    size_t lds = (size_t)ld * sizeof(float) * 2;
-    if (order == MN_ORDER_SSE_V) {
-        hipLaunchKernelGGL((k_dist_batch<MN_ORDER_SSE_V, 0>), grid, block, lds, st, metric, d_query, d_rows, n, dim, ld, d_out);
-        return;
-    }
+        return 0;
+    if (order == MN_ORDER_SSE_V)
+        return launch_dist_batch<MN_ORDER_SSE_V, 0>(metric, d_query, d_rows, n, dim, ld, d_out, st);
 #define MN_DB(N) \
     case N:      \
-        hipLaunchKernelGGL((k_dist_batch<MN_ORDER_WAVE_V, N>), grid, block, lds, st, metric, d_query, d_rows, n, dim, ld, d_out); \
-        break;
+        return launch_dist_batch<MN_ORDER_WAVE_V, N>(metric, d_query, d_rows, n, dim, ld, d_out, st);
     switch (pick_nch(ld)) {
         MN_DB(1) MN_DB(2) MN_DB(3) MN_DB(4) MN_DB(6) MN_DB(8)
     default:
-        hipLaunchKernelGGL((k_dist_batch<MN_ORDER_WAVE_V, 0>), grid, block, lds, st, metric, d_query, d_rows, n, dim, ld, d_out);
+        return launch_dist_batch<MN_ORDER_WAVE_V, 0>(metric, d_query, d_rows, n, dim, ld, d_out, st);
     }
 #undef MN_DB
 }
@@ -401,6 +411,8 @@ size_t mn_search_lds_bytes(int ld, bool tile) {
         b += (size_t)atoi(pad);
     return b;
 }
+// k_beam_coop without its optional parts (distance tiles and the visited bitmap are added only where they fit)
+size_t mn_coop_lds_bytes(int ld, bool tile) { return ((mn_search_lds_bytes(ld, tile) + 15) & ~(size_t)15) + (4 + 64 + 64) * sizeof(int); }
 
 // Dynamic LDS beyond 64 KB has to be asked for per kernel (hipFuncAttributeMaxDynamicSharedMemorySize); what the device would
 // grant is asked once.  Anything that fails leaves the 64 KB every kernel gets.
@@ -465,12 +477,12 @@ static void launch_coop(const MnDevIndex &ix, MnSearchArgs a, size_t base, size_
                 a.lat_tile_rows = rows;
                 a.lat_tile_off = (unsigned)off;
                 tot = need;
-                if (getenv("MN_LAT_DEBUG"))
-                    fprintf(stderr, "[mn] k_beam_coop: distance tile of %d rows per wavefront, %zu bytes of LDS\n", rows, need);
                 break;
             }
         }
     }
+    if (getenv("MN_LAT_DEBUG"))
+        fprintf(stderr, "[mn] k_beam_coop: distance tile of %d rows per wavefront, %zu bytes of LDS\n", a.lat_tile_rows, tot);
     hipLaunchKernelGGL((k_beam_coop<ORDER, NCH, BUILD, WIDE>), dim3((unsigned)a.nq), dim3(MN_COOP_WAVES * 64), tot, st, ix, a, base);
 }
 
@@ -482,7 +494,8 @@ static void launch_beam(const MnDevIndex &ix, const MnSearchArgs &a, bool build,
     const char *co = getenv("MN_COOP"); // MN_COOP=0: always one wavefront per query
     if (a.nq <= 128 && !(co && atoi(co) == 0)) {
         const size_t base = (lds + 15) & ~(size_t)15;
-        const size_t tot = base + (4 + 64 + 64) * sizeof(int) + (!build && a.lds_bitmap ? (size_t)a.bm0_words * sizeof(unsigned) : 0);
+        const size_t tot = mn_coop_lds_bytes(ix.ld, ORDER == MN_ORDER_SSE_V && a.use_tile) +
+                           (!build && a.lds_bitmap ? (size_t)a.bm0_words * sizeof(unsigned) : 0);
         if (wide) {
             if (build)
                 launch_coop<ORDER, NCH, true, true>(ix, a, base, tot, st);
@@ -582,7 +595,7 @@ void mn_launch_edge_rows(const MnDevIndex &ix, const int *d_row_slot, const int 
                          float *d_out_dist, hipStream_t st) {
     if (n_rows <= 0)
         return;
-    size_t lds = (size_t)ix.ld * sizeof(float);
+    size_t lds = mn_row_lds_bytes(ix.ld);
     dim3 grid(n_rows), block(64);
 #define MN_ER(O, N) hipLaunchKernelGGL((k_edge_rows<O, N>), grid, block, lds, st, ix, d_row_slot, d_row_level, n_rows, d_out_nbr, d_out_dist)
     if (ix.order == MN_ORDER_SSE_V) {

@@ -465,6 +465,9 @@ void mn_launch_insert_seq(const MnDevIndex &ix, const int *d_slots, int n, int e
                     (void)mn_lds_grant(kp, lds); /* the kernel's own arrays alone pass 64 KB: refused = the launch fails */  \
             }                                                                                                                \
         }                                                                                                                    \
+        if (getenv("MN_LAT_DEBUG"))                                                                                          \
+            fprintf(stderr, "[mn] k_insert_seq: distance tile of %d rows per wavefront, %zu bytes of LDS\n", a.lat_tile_rows,  \
+                    lds);                                                                                                    \
         if (ix.WX > 64)                                                                                                      \
             hipLaunchKernelGGL((k_insert_seq<O, N, true>), dim3(1), blk, lds, st, ix, a, base);                              \
         else                                                                                                                 \

@@ -459,6 +459,11 @@ static int pick_nch_p(int ld) {
     return 0;
 }
 
+#define MN_SPEC_SHARED_BYTES ((16 + 64 + 64 + 64 + 64 * 64) * sizeof(int))
+static size_t spec_wave_bytes(int ld) { return (3 * 128 * sizeof(int) + (size_t)ld * sizeof(float) + 15) & ~(size_t)15; }
+// k_spec_commit with its one wavefront (it never asks for more than 64 KB)
+size_t mn_spec_commit_min_lds_bytes(int ld) { return MN_SPEC_SHARED_BYTES + spec_wave_bytes(ld); }
+
 // one workgroup; as many wavefronts as 60 KB of LDS allow (≤ 8)
 void mn_launch_spec_commit(const MnDevIndex &ix, const int *d_slots, int W, int nlev, const int *sel, const int *nsel,
                            const int *readlog, int readcap, const int *nread, int *stamp0, int *stampU, int *sidx0, int *sidxU,
@@ -484,11 +489,10 @@ void mn_launch_spec_commit(const MnDevIndex &ix, const int *d_slots, int W, int 
     a.why = why;
     a.epoch = epoch;
     a.ncommit = d_ncommit;
-    a.wave_bytes = (3 * 128 * sizeof(int) + (size_t)ix.ld * sizeof(float) + 15) & ~(size_t)15;
-    const size_t shared = (16 + 64 + 64 + 64 + 64 * 64) * sizeof(int);
-    int nw = (int)((60 * 1024 - shared) / a.wave_bytes);
+    a.wave_bytes = spec_wave_bytes(ix.ld);
+    int nw = (int)((60 * 1024 - MN_SPEC_SHARED_BYTES) / a.wave_bytes);
     nw = nw < 1 ? 1 : (nw > MN_SPEC_MAX_WAVES ? MN_SPEC_MAX_WAVES : nw);
-    const size_t lds = shared + (size_t)nw * a.wave_bytes;
+    const size_t lds = MN_SPEC_SHARED_BYTES + (size_t)nw * a.wave_bytes;
     const size_t lds_pre = (size_t)nw * a.wave_bytes;
 #define MN_SP(O, N)                                                                                                              \
     do {                                                                                                                         \

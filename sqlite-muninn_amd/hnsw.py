@@ -51,6 +51,7 @@ SYMBOLS = [
     ("mn_vec_dist_batch", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, C.c_int64, C.c_int, _f32p]),
     ("mn_hnsw_create", C.c_void_p, [C.c_int] * 4),
     ("mn_hnsw_create_on", C.c_void_p, [C.c_int] * 5),
+    ("mn_hnsw_max_dim", C.c_int, [C.c_int, C.c_int]),
     ("mn_hnsw_destroy", None, [C.c_void_p]),
     ("mn_hnsw_seed_rng", None, [C.c_void_p, C.c_uint]),
     ("mn_hnsw_set_order", C.c_int, [C.c_void_p, C.c_int]),
@@ -164,6 +165,14 @@ def vec_dist_batch(metric: str, query, rows, order: int = ORDER_SSE) -> np.ndarr
     if lib().mn_vec_dist_batch(METRIC[metric], order, q, r, r.shape[0], q.shape[0], out) != 0:
         raise MuninnHipError(_err())
     return out
+
+
+def max_dim(M: int = 16, device: int = 0) -> int:
+    """The largest dim an index with this M can have on this device (mn_hnsw_max_dim)."""
+    v = lib().mn_hnsw_max_dim(M, device)
+    if v < 0:
+        raise MuninnHipError(_err())
+    return v
 
 
 class ShardedIndex:

@@ -4,7 +4,7 @@ oracle running the same summation order, and within 1e-5 relative of the referen
 import numpy as np
 import pytest
 
-from util import gauss, same_bits
+from util import check_topk_f64, gauss, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -620,9 +620,10 @@ def test_node_table_fills_under_churn_as_in_the_reference(gpu, orc):
 @pytest.mark.parametrize("metric", METRICS)
 @pytest.mark.parametrize("n,dim,nq,k", [(5000, 50, 300, 10), (1111, 7, 5, 1), (20000, 768, 130, 16)])
 def test_mfma_bruteforce_ground_truth(gpu, metric, n, dim, nq, k, monkeypatch):
-    """k_brute_mfma (the dense query x row block on the f32 matrix cores + fused top-k) against float64 numpy and against
-    the VALU kernel that uses the index's own inner loop: identical id lists except where two distances differ by
-    rounding only (different summation orders) — counted, and bounded."""
+    """k_brute_mfma (the dense query x row block on the f32 matrix cores + fused top-k) and the VALU kernel that uses the
+    index's own inner loop, each against float64 numpy: every returned row within rounding (a per-pair bound from the f32
+    operation count) of the k-th distance, every row clearly nearer returned, the list ordered up to rounding
+    (util.check_topk_f64)."""
     X = gauss(n, dim, 21)
     X[17] = X[3]  # exact duplicate rows: ties resolve to the lower row
     Q = gauss(nq, dim, 22)
@@ -638,19 +639,9 @@ def test_mfma_bruteforce_ground_truth(gpu, metric, n, dim, nq, k, monkeypatch):
     monkeypatch.setenv("MN_BRUTE", "valu")
     valu = g.bruteforce_topk(dq, nq, k)
     monkeypatch.delenv("MN_BRUTE")
-    X64, Q64 = X.astype(np.float64), Q.astype(np.float64)
-    if metric == "l2":
-        D = (Q64 ** 2).sum(1)[:, None] + (X64 ** 2).sum(1)[None, :] - 2 * Q64 @ X64.T
-    elif metric == "cosine":
-        D = 1 - (Q64 @ X64.T) / (np.linalg.norm(Q64, axis=1)[:, None] * np.linalg.norm(X64, axis=1)[None, :])
-    else:
-        D = -(Q64 @ X64.T)
-    D[:, [5, 40]] = np.inf
-    want = ids[np.argsort(D, axis=1, kind="stable")[:, :k]]
     assert not np.isin(got, [105, 140]).any() and (got >= 100).all()
-    agree64 = np.mean([len(set(got[i]) & set(want[i])) / k for i in range(nq)])
-    agreev = np.mean([len(set(got[i]) & set(valu[i])) / k for i in range(nq)])
-    assert agree64 >= 0.995 and agreev >= 0.995, (agree64, agreev)
+    check_topk_f64(got, X, Q, ids, np.array([105, 140], np.int64), k, metric)
+    check_topk_f64(valu, X, Q, ids, np.array([105, 140], np.int64), k, metric)
     assert got[0][0] in (103, 117) and (k == 1 or set(got[0][:2]) == {103, 117})  # the duplicated row, both copies
     g.dev_free(dq)
     g.close()
@@ -903,8 +894,9 @@ print("OK")
 @pytest.mark.parametrize("knob", ["MN_LDS_OPTIN", "MN_LAT_TILE", "MN_SEQ_PRE", "MN_COOP", "MN_SPECULATE"])
 def test_latency_kernel_fallbacks_give_the_same_graph_and_answers(gpu, knob):
     """The lone-search / lone-insert kernels pick their LDS geometry at launch: a 4-row distance tile per wavefront when the device
-    grants more than 64 KB (else 2 rows, else none), precomputed prune distances when they fit, helper wavefronts.  Every knob
-    that switches one of these off (MN_LDS_OPTIN=0 is the only way the 2-row tile is reached on this part: 512-d) must leave the
+    grants room for it (else 2 rows, else none), precomputed prune distances when they fit, helper wavefronts.  Every knob
+    that switches one of these off (MN_LDS_OPTIN=0 takes 512-d to the 2-row tile; with the 160 KB opt-in of this part the 2-row
+    tile is taken from about 950 floats and none above about 1500 — test_row_lengths.py asserts each) must leave the
     graph of one-at-a-time inserts and the answers of one-at-a-time queries equal to the oracle's, bit for bit (ids, distance
     bits), at dimensions that use the tile (768, 512, 300) and one that does not (24)."""
     import os

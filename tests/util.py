@@ -43,3 +43,39 @@ def overgrown_case(mk, long_lists=True):
                 extra = rng.choice(cand, min(len(cand), 3 * (2 * M if l == 0 else M)), replace=False)
                 assert x.load_neighbors(i, l, np.asarray(extra, np.int64)) == 0
     return x, ids, X, grown
+
+
+def check_topk_f64(got, X, Q, ids, deleted, k, metric, c=4.0):
+    """Rounding-aware comparison of a top-k id list with float64 distances.  eps bounds one pair's f32 error:
+    c·dim·2⁻²⁴·(|q|²+|x|²) (l2), c·dim·2⁻²⁴ (cosine), c·dim·2⁻²⁴·|q||x| (inner product)."""
+    X64, Q64 = X.astype(np.float64), Q.astype(np.float64)
+    dim = X.shape[1]
+    u = 2.0 ** -24
+    qn, xn = np.linalg.norm(Q64, axis=1), np.linalg.norm(X64, axis=1)
+    if metric == "l2":
+        D = (qn ** 2)[:, None] + (xn ** 2)[None, :] - 2 * Q64 @ X64.T
+        E = c * dim * u * ((qn ** 2)[:, None] + (xn ** 2)[None, :])
+    elif metric == "cosine":
+        D = 1 - (Q64 @ X64.T) / np.maximum(qn[:, None] * xn[None, :], 1e-300)
+        E = np.full(D.shape, c * dim * u)
+    else:
+        D = -(Q64 @ X64.T)
+        E = c * dim * u * (qn[:, None] * xn[None, :])
+    live = np.ones(len(ids), bool)
+    live[[int(np.searchsorted(ids, d)) for d in deleted]] = False
+    n_live = int(live.sum())
+    for i in range(len(Q)):
+        row = got[i]
+        kk = min(k, n_live)
+        assert (row[kk:] == -1).all() and (row[:kk] >= 0).all(), (i, row)
+        r = row[:kk]
+        assert len(set(r.tolist())) == kk, (i, r)
+        assert not np.isin(r, deleted).any(), (i, r)
+        pos = np.searchsorted(ids, r)
+        assert (ids[pos] == r).all(), (i, r)
+        d, e = D[i], E[i]
+        kth = np.sort(d[live])[kk - 1]
+        assert (d[pos] <= kth + e[pos]).all(), (i, r, d[pos] - kth, e[pos])
+        must = np.nonzero(live & (d < kth - e))[0]
+        assert np.isin(must, pos).all(), (i, np.setdiff1d(must, pos))
+        assert (d[pos][:-1] <= d[pos][1:] + e[pos][:-1] + e[pos][1:]).all(), (i, r)
