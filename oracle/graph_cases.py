@@ -56,7 +56,9 @@ TWO_CLIQUES = [(1, 2), (1, 3), (1, 4), (2, 3), (2, 4), (3, 4), (5, 6), (5, 7), (
 
 def n2v_cases():
     """name -> (edges, (dim, p, q, num_walks, walk_length, window, neg, lr, epochs)); parameters of
-    pytests/test_node2vec.py:160,203,233 plus p/q != 1 variants and a random graph with isolated-ish nodes."""
+    pytests/test_node2vec.py:160,203,233 plus p/q != 1 variants and a random graph with isolated-ish nodes; then the
+    widths and lengths at the edges of k_n2v_seq: dim 1, 257 (5 register slots per lane), 1024 (16 slots, the largest
+    LDS layout) and a walk longer than N2V_LDS_WALK = 4096 (kept in global scratch)."""
     er_s, er_d, _ = er(60, 150, 11)
     return {
         "cliques16": (TWO_CLIQUES, (16, 1.0, 1.0, 5, 20, 3, 3, 0.025, 3)),
@@ -65,6 +67,10 @@ def n2v_cases():
         "karate64": (KARATE, (64, 1.0, 1.0, 10, 80, 5, 5, 0.025, 5)),
         "karate_pq": (KARATE, (12, 0.25, 4.0, 3, 30, 4, 3, 0.025, 2)),
         "er60_dim70": ([(int(a), int(b)) for a, b in zip(er_s, er_d)], (70, 2.0, 0.5, 2, 25, 3, 4, 0.03, 1)),
+        "cliques_d1": (TWO_CLIQUES, (1, 1.0, 1.0, 4, 20, 3, 3, 0.025, 2)),
+        "karate_d257_pq": (KARATE, (257, 0.5, 2.0, 2, 20, 3, 3, 0.025, 1)),
+        "cliques_d1024": (TWO_CLIQUES, (1024, 1.0, 1.0, 2, 15, 2, 2, 0.025, 1)),
+        "cliques_walk4100": (TWO_CLIQUES, (8, 1.0, 1.0, 1, 4100, 2, 2, 0.025, 1)),
     }
 
 

@@ -672,7 +672,7 @@ int orc_node2vec_train(const orc_n2v_graph *g, const orc_n2v_params *p, float *o
     float *syn1neg = (float *)calloc((size_t)N * dim, sizeof(float));
     int *neg_table = (int *)malloc(N2V_NEG_TABLE * sizeof(int));
     float *neu1e = (float *)malloc((size_t)dim * sizeof(float));
-    int *walk = (int *)malloc((size_t)p->walk_length * sizeof(int));
+    int *walk = (int *)malloc((size_t)(p->walk_length > 2 ? p->walk_length : 2) * sizeof(int)); /* walk[1] is stored first */
     for (int i = 0; i < N * dim; i++) /* :323-325 */
         syn0[i] = ((float)n2v_rand(&rng) - 0.5f) / (float)dim;
     orc_n2v_neg_table(g, neg_table);
@@ -775,7 +775,7 @@ int orc_node2vec_train_batched(const orc_n2v_graph *g, const orc_n2v_params *p, 
     float *old0 = (float *)malloc((size_t)N * dim * sizeof(float));
     float *old1 = (float *)malloc((size_t)N * dim * sizeof(float));
     int *neg_table = (int *)malloc(N2V_NEG_TABLE * sizeof(int));
-    int *walk = (int *)malloc((size_t)p->walk_length * sizeof(int));
+    int *walk = (int *)malloc((size_t)(p->walk_length > 2 ? p->walk_length : 2) * sizeof(int)); /* walk[1] is stored first */
     float *neu = (float *)malloc((size_t)dim * sizeof(float));
     for (int i = 0; i < N * dim; i++)
         syn0[i] = ((float)n2v_rand(&rng) - 0.5f) / (float)dim;

@@ -51,7 +51,8 @@ typedef struct {
 int orc_node2vec_train(const orc_n2v_graph *g, const orc_n2v_params *p, float *out, int64_t *n_pairs);
 /* the batch-synchronous schedule of the HIP MN_N2V_BATCHED mode (B walks per batch) */
 int orc_node2vec_train_batched(const orc_n2v_graph *g, const orc_n2v_params *p, int B, float *out, int64_t *n_pairs);
-/* biased_walk (src/node2vec.c:168-226) from an explicit rng state; returns the walk length */
+/* biased_walk (src/node2vec.c:168-226) from an explicit rng state; returns the walk length.  walk[] must hold
+   max(walk_length, 2) ints: as in the reference, walk[1] is stored before walk_length is looked at (:178) */
 int orc_biased_walk(const orc_n2v_graph *g, int start, double p, double q, int walk_length, int *walk, unsigned *rng);
 /* Builds the reference's Graph from an edge list (first-seen indices, undirected, de-duplicated);
  * returns n; off must hold n_max+1 ints, adj 2*n_edges ints, index_of_id n_ids ints (or NULL). */

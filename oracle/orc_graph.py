@@ -165,6 +165,17 @@ class N2vGraph:
         self.adj = adj[:self.off[-1]].copy() if self.n else np.zeros(0, np.int32)
         self.index_of_id = idx[:n_ids]
 
+    @classmethod
+    def from_csr(cls, off, adj):
+        """A graph given as CSR directly (node i = index i): isolated nodes and one-way edges into a dead end, which no
+        edge table can express, reach the walks through the C ABI."""
+        g = cls.__new__(cls)
+        g.off = np.ascontiguousarray(off, np.int32)
+        g.adj = np.ascontiguousarray(adj, np.int32)
+        g.n = len(g.off) - 1
+        g.index_of_id = np.arange(g.n, dtype=np.int32)
+        return g
+
     def c_struct(self):
         g = _N2vGraph()
         g.n = self.n
@@ -193,7 +204,7 @@ def node2vec_train_batched(g: N2vGraph, dim, p, q, num_walks, walk_length, windo
 
 
 def biased_walk(g: N2vGraph, start, p, q, walk_length, rng_state):
-    walk = np.zeros(walk_length, np.int32)
+    walk = np.zeros(max(walk_length, 2), np.int32)  # orc_biased_walk stores walk[1] before it looks at walk_length
     st = C.c_uint(rng_state)
     cg = g.c_struct()
     n = _n2v_lib().orc_biased_walk(C.byref(cg), start, p, q, walk_length, walk, C.byref(st))

@@ -54,6 +54,16 @@ DEVI void cum_st(double *lds, double *glb, bool in_lds, int i, double v) {
     else
         __hip_atomic_store(glb + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// the walk: LDS when it fits, else the session's walk scratch through L2 (sc1) — the slots are rewritten every walk
+DEVI int walk_ld(const int *lds, const int *glb, bool in_lds, int i) {
+    return in_lds ? lds[i] : __hip_atomic_load(glb + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEVI void walk_st(int *lds, int *glb, bool in_lds, int i, int v) {
+    if (in_lds)
+        lds[i] = v;
+    else
+        __hip_atomic_store(glb + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 DEVI void stf(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct N2vArgs {
@@ -66,7 +76,7 @@ struct N2vArgs {
     double p, q, lr;
     unsigned rng;
     double *cum_scratch; // [max_deg] for nodes with more than N2V_LDS_DEG neighbours
-    int *walk_scratch;   // [walk_length] when longer than N2V_LDS_WALK
+    int *walk_scratch;   // [walk_length], used when longer than N2V_LDS_WALK
     unsigned long long *out; // [0] pairs, [1] final rng
 };
 
@@ -91,8 +101,9 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
     float *vc = prod + a.dim;                                     // [dim]
     float *neu = vc + a.dim;                                      // [dim]
     float *sig = neu + a.dim;                                     // [1001]
-    int *walk_l = reinterpret_cast<int *>(sig + N2V_SIG_SIZE + 1);
-    int *walk = walk_l; // LDS (walk_length <= N2V_LDS_WALK is enforced by the host)
+    int *walk_l = reinterpret_cast<int *>(sig + N2V_SIG_SIZE + 1); // [walk_length] when it fits, else a.walk_scratch
+    int *walk_g = a.walk_scratch;
+    const bool walk_in_lds = a.walk_length <= N2V_LDS_WALK;
     for (int i = lane; i <= N2V_SIG_SIZE; i += 64)
         sig[i] = a.sig_table[i];
     __builtin_amdgcn_s_waitcnt(0);
@@ -113,7 +124,7 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
                 int wlen;
                 {
                     if (lane == 0)
-                        walk[0] = n;
+                        walk_st(walk_l, walk_g, walk_in_lds, 0, n);
                     const int s0 = a.off[n], deg0 = a.off[n + 1] - s0;
                     if (deg0 == 0) {
                         wlen = 1;
@@ -123,7 +134,7 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
                             idx = deg0 - 1;
                         int cur = a.adj[s0 + idx], prev = n;
                         if (lane == 0)
-                            walk[1] = cur;
+                            walk_st(walk_l, walk_g, walk_in_lds, 1, cur);
                         wlen = a.walk_length;
                         for (int step = 2; step < a.walk_length; step++) {
                             const int c0 = a.off[cur], deg = a.off[cur + 1] - c0;
@@ -175,7 +186,7 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
                             }
                             const int chosen = chosen_i == 0x7fffffff ? a.adj[c0] : a.adj[c0 + chosen_i]; // fallback :202
                             if (lane == 0)
-                                walk[step] = chosen;
+                                walk_st(walk_l, walk_g, walk_in_lds, step, chosen);
                             prev = cur;
                             cur = chosen;
                         }
@@ -185,7 +196,7 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
                 __builtin_amdgcn_wave_barrier();
                 // ── skip-gram over the walk (:517-533) ──
                 for (int pos = 0; pos < wlen; pos++) {
-                    const int center = walk[pos];
+                    const int center = walk_ld(walk_l, walk_g, walk_in_lds, pos);
                     int cs = pos - a.window, ce = pos + a.window;
                     if (cs < 0)
                         cs = 0;
@@ -195,7 +206,7 @@ __global__ void __launch_bounds__(64) k_n2v_seq(N2vArgs a) {
                     for (int c = cs; c <= ce; c++) {
                         if (c == pos)
                             continue;
-                        const int context = walk[c];
+                        const int context = walk_ld(walk_l, walk_g, walk_in_lds, c);
                         // sgns_train_pair (:345-394)
                         __builtin_amdgcn_wave_barrier();
                         for (int d = lane; d < dim; d += 64) {
@@ -837,10 +848,6 @@ extern "C" int mn_node2vec_train(int n, const int *off, const int *adj, const mn
         mn_n2v_end(S);
         return rc < 0 ? -1 : n;
     }
-    if (prm->walk_length > N2V_LDS_WALK) {
-        nset_err("mn_node2vec_train: walk_length %d exceeds %d", prm->walk_length, N2V_LDS_WALK);
-        return -1;
-    }
     if (mode != MN_N2V_SEQUENTIAL) {
         nset_err("mn_node2vec_train: mode %d not available", mode);
         return -1;
@@ -850,8 +857,10 @@ extern "C" int mn_node2vec_train(int n, const int *off, const int *adj, const mn
     if (session_init(S, n, off, adj, prm, device, false) != 0)
         return -1;
     const int dim = prm->dim;
+    // (a walk longer than N2V_LDS_WALK lives in a.walk_scratch; walk[1] is stored before walk_length is looked at, :178)
+    const int walk_lds = prm->walk_length <= N2V_LDS_WALK ? std::max(prm->walk_length, 2) : 0;
     size_t lds = N2V_LDS_DEG * sizeof(double) + 3 * (size_t)dim * sizeof(float) + (N2V_SIG_SIZE + 1) * sizeof(float) +
-                 (size_t)std::min(prm->walk_length, N2V_LDS_WALK) * sizeof(int) + 64;
+                 (size_t)walk_lds * sizeof(int) + 64;
     NCHK(hipEventRecord(S->e0, S->st));
     hipLaunchKernelGGL(k_n2v_seq, dim3(1), dim3(64), lds, S->st, S->a);
     NCHK(hipGetLastError());

@@ -19,6 +19,71 @@ def _graph(edges):
     return og.N2vGraph(e[:, 0], e[:, 1])
 
 
+def _star(leaves):
+    """a hub (first-seen index 0) and `leaves` leaves whose only neighbour is the hub"""
+    return _graph([(0, i) for i in range(1, leaves + 1)])
+
+
+def _dead_end_graph(n=203, seed=5):
+    """n nodes of an undirected random graph (mean degree ~6) in which at least six nodes are isolated (walks of one
+    node) and three are dead ends: their neighbours list them, they list nobody, so a walk that reaches one ends there,
+    at any step.  Given as CSR (node i = index i): an edge table can express neither."""
+    r = np.random.default_rng(seed)
+    isolated, dead = {0, 9, 64, 65, 131, n - 1}, {17, 100, 150}
+    lists = [[] for _ in range(n)]
+    for a, b in r.integers(0, n, (3 * n, 2)).tolist():
+        if a != b and a not in isolated and b not in isolated and b not in lists[a]:
+            lists[a].append(b)
+            lists[b].append(a)
+    for d in dead:
+        lists[d] = []
+    off = np.concatenate([[0], np.cumsum([len(x) for x in lists])])
+    return og.N2vGraph.from_csr(off, [x for lst in lists for x in lst])
+
+
+def _n2v_template(dim):
+    """N2V_DISPATCH (csrc/mn_n2v_batched.hpp) → (NR register slots per lane, PF target rows in flight per chunk in
+    k_n2v_walk_grad, U source rows in flight in k_n2v_apply)"""
+    nr = (dim + 63) // 64
+    NR = next(t for t in (1, 2, 4, 8, 16) if nr <= t)
+    return NR, 6 if NR <= 4 else 2, 8 if NR <= 2 else 4 if NR <= 4 else 1
+
+
+def _n2v_split(p, q, walk_length, walks):
+    """wavefronts that share one walk in k_n2v_walk_grad (n2v_samples_t), for a batch of `walks` walks"""
+    split = -(-32768 // walks) if p == 1.0 and q == 1.0 else 1
+    return max(1, min(split, 8, walk_length))
+
+
+def _seq_vs_oracle(gpu, g, prm):
+    want, npairs = og.node2vec_train(g, *prm)
+    got, st = gpu.node2vec_train(g.off, g.adj, *prm)
+    assert st["pairs"] == npairs
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    return npairs
+
+
+def _batched_vs_oracle(gpu, g, prm, batch):
+    want, npairs = og.node2vec_train_batched(g, *prm, batch)
+    got, st = gpu.node2vec_train(g.off, g.adj, *prm, mode=gpu.N2V_BATCHED, batch_walks=batch)
+    assert st["pairs"] == npairs
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    return npairs
+
+
+# walks of 3 nodes on a star: every leaf's walk takes its step 2 on the hub
+HUB_PRM = [(8, 1.0, 1.0, 1, 3, 2, 2, 0.025, 1), (8, 0.5, 2.0, 1, 3, 2, 2, 0.025, 1)]
+
+# (dim, p, q, neg) for the batched schedule: every NR template at its lower edge, when full and with idle register slots;
+# within each PF class runs of full chunks only ((1 + neg) % PF == 0) and runs that end in a partial chunk
+WIDTHS = [(1, 1.0, 1.0, 5), (63, 0.5, 2.0, 6), (64, 1.0, 1.0, 1), (65, 0.5, 2.0, 5), (128, 1.0, 1.0, 6), (129, 0.5, 2.0, 1),
+          (192, 1.0, 1.0, 5), (256, 0.5, 2.0, 6), (257, 1.0, 1.0, 1), (384, 0.5, 2.0, 2), (512, 1.0, 1.0, 5),
+          (513, 0.5, 2.0, 2), (768, 1.0, 1.0, 1), (1000, 0.5, 2.0, 5), (1024, 1.0, 1.0, 2)]
+
+# (walk_length, batch_walks) with p = q = 1: split 8, 3, 2 and 1
+SPLITS = [(20, 5), (3, 64), (2, 64), (1, 64)]
+
+
 def _within_between(emb, index_of_id, a_ids, b_ids):
     def cos(x, y):
         return float(np.dot(x, y) / (np.linalg.norm(x) * np.linalg.norm(y)))
@@ -65,6 +130,32 @@ def test_walk_properties():
         assert b in g.adj[g.off[a]:g.off[a + 1]]
     walk2, st2 = og.biased_walk(g, 0, 0.5, 2.0, 40, 12345)
     assert np.array_equal(walk, walk2) and st == st2
+    for wl in (1, 2):  # walk[1] is stored before walk_length is looked at (src/node2vec.c:178)
+        walk, _ = og.biased_walk(g, 0, 0.5, 2.0, wl, 12345)
+        assert len(walk) == wl and walk[0] == 0
+
+
+def test_live_reference_star_2049_leaves():
+    """the oracle against the compiled reference on a hub one past k_n2v_seq's LDS limit (N2V_LDS_DEG = 2048)"""
+    if not og.have_ref_graph():
+        pytest.skip("compiled reference not present")
+    edges = [(0, i) for i in range(1, 2050)]
+    for prm in HUB_PRM:
+        want = og.ref_node2vec_sql(edges, *prm)
+        got, _ = og.node2vec_train(_graph(edges), *prm)
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), prm
+
+
+def test_width_cases_cover_every_template_and_chunk_shape():
+    """WIDTHS reaches every instantiation of N2V_DISPATCH, each with a run of full chunks only and one that ends in a
+    partial chunk; SPLITS reaches split 1, 2, 3 and 8."""
+    seen = set()
+    for dim, p, q, neg in WIDTHS:
+        nr, pf, _ = _n2v_template(dim)
+        seen.add((nr, (1 + neg) % pf == 0))
+    assert seen == {(nr, full) for nr in (1, 2, 4, 8, 16) for full in (True, False)}
+    assert {(p, q) for _, p, q, _ in WIDTHS} == {(1.0, 1.0), (0.5, 2.0)}
+    assert {_n2v_split(1.0, 1.0, wl, b) for wl, b in SPLITS} == {1, 2, 3, 8}
 
 
 # ───────────────────────── GPU ─────────────────────────
@@ -183,12 +274,13 @@ def test_config4_shape_properties_200k_nodes(gpu):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [64, 30])
+@pytest.mark.parametrize("dim", [64, 30, 256, 301])
 def test_train_into_index_keeps_the_embeddings_in_hbm_and_builds_the_same_graph(gpu, dim):
     """mn_node2vec_train_into (config 4's "-> hnsw0 index" leg, src/node2vec.c:540-583): the embeddings are trained, normalised
     and handed to the index build inside HBM.  Same embedding bytes as mn_node2vec_train in the same mode, and the index is the
     graph mn_hnsw_build makes from a host copy of those embeddings with the reference's rowids (first-seen index + 1).
-    (dim 30: the index pads rows to 32 floats, so the device-to-device hand-off is a strided copy.)"""
+    (dim 30 and 301: the index pads rows to a multiple of 4 floats, so the device-to-device hand-off is a strided copy;
+    dim 256: the index also keeps its fp16 shadow of the rows.)"""
     from oracle.graph_cases import planted
 
     s, d, _ = planted(3000, 6, 0.05, 0.001, 11)
@@ -207,3 +299,84 @@ def test_train_into_index_keeps_the_embeddings_in_hbm_and_builds_the_same_graph(
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32))
     ix.close()
     ref.close()
+
+
+# ───────────────────────── GPU: widths, hubs and walk shapes at the edges of the kernels ─────────────────────────
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("leaves", [2048, 2049])
+@pytest.mark.parametrize("prm", HUB_PRM, ids=["uniform", "pq"])
+def test_gpu_sequential_hub_at_the_lds_limit(gpu, leaves, prm):
+    """k_n2v_seq keeps a step's running totals in LDS up to N2V_LDS_DEG = 2048 neighbours and in global scratch above
+    (the totals are also summed there when p = q = 1).  Every leaf's walk takes a step on the hub."""
+    _seq_vs_oracle(gpu, _star(leaves), prm)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wl", [1, 2])
+def test_gpu_sequential_walk_length_1_and_2(gpu, wl):
+    """The shortest walks, on a graph with isolated nodes (walks of one node).  A walk of 2 nodes has 2 pairs.  (No reference
+    golden: the reference writes walk[1] past its buffer of walk_length ints, src/node2vec.c:178.)"""
+    g = _dead_end_graph()
+    npairs = _seq_vs_oracle(gpu, g, (16, 0.5, 2.0, 2, wl, 2, 3, 0.025, 1))
+    assert npairs == (0 if wl == 1 else 2 * 2 * np.count_nonzero(np.diff(g.off)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,p,q,neg", WIDTHS)
+def test_gpu_batched_every_width_bit_exact(gpu, dim, p, q, neg):
+    """k_n2v_walk_grad, k_n2v_apply and k_n2v_apply_centers at every NR template (see WIDTHS), batches of 64 walks of
+    203 nodes (the last batch has 11)."""
+    _batched_vs_oracle(gpu, _dead_end_graph(), (dim, p, q, 1, 10, 2, neg, 0.025, 1), 64)
+
+
+def _hub_graph():
+    """a ring of 1 500 nodes plus hubs of exactly 512, 513 and 1 500 neighbours on it"""
+    n = 1500
+    edges = [(i, (i + 1) % n) for i in range(n)] + [(n, i) for i in range(512)] + [(n + 1, i) for i in range(513)]
+    return _graph(edges + [(n + 2, i) for i in range(n)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,neg", [(65, 6), (513, 2)])
+@pytest.mark.parametrize("p,q", [(0.5, 2.0), (1.0, 1.0)])
+def test_gpu_batched_hubs_at_the_lds_limit(gpu, dim, neg, p, q):
+    """The biased walk keeps a step's running totals in LDS up to N2VB_LDS_DEG = 512 neighbours and in per-walk global
+    scratch above; p = q = 1 takes the closed form instead.  One dim of each PF class."""
+    g = _hub_graph()
+    assert sorted(np.diff(g.off))[-3:] == [512, 513, 1500]
+    _batched_vs_oracle(gpu, g, (dim, p, q, 1, 8, 2, neg, 0.025, 1), 100)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [65, 513])
+def test_gpu_batched_hub_row_over_64_samples_per_batch(gpu, dim):
+    """k_n2v_apply reads a row's samples 64 at a time and folds U of them at once (U = 8 at dim 65, 1 at dim 513).  On a
+    star whose leaves have only the hub as neighbour, every walk has the hub at position 1 (the hub's own walk at 0).  With 2
+    nodes per walk and window 1, a walk's pairs are (start, hub) and (hub, start): the first gives the hub row exactly one
+    sample, its positive (a negative that draws the hub is dropped as the context), the second none (the hub is the
+    centre).  So the hub row gets one sample per walk of the batch: 141 = 64 + 64 + 13 in each full batch of 141, and 13 is
+    not a multiple of U.  Walks of 6 nodes with window 2 and p != q then give it several per walk."""
+    g = _star(299)
+    assert _batched_vs_oracle(gpu, g, (dim, 1.0, 1.0, 1, 2, 1, 5, 0.025, 1), 141) == 2 * g.n
+    _batched_vs_oracle(gpu, g, (dim, 0.5, 2.0, 1, 6, 2, 2, 0.025, 1), 141)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,neg", [(65, 5), (513, 2)])
+@pytest.mark.parametrize("wl,batch", SPLITS)
+def test_gpu_batched_split_walks(gpu, dim, neg, wl, batch):
+    """`split` wavefronts share one walk, each owning a range of its positions.  Isolated nodes and dead ends end walks
+    before most parts start; 203 walks in batches of 64 (or 5) end in a short batch."""
+    g = _dead_end_graph()
+    npairs = _batched_vs_oracle(gpu, g, (dim, 1.0, 1.0, 2, wl, 3, neg, 0.025, 1), batch)
+    if wl <= 2:
+        assert npairs == (0 if wl == 1 else 2 * 2 * np.count_nonzero(np.diff(g.off)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [65, 513])
+@pytest.mark.parametrize("p,q", [(1.0, 1.0), (0.5, 2.0)])
+def test_gpu_batched_walk_longer_than_4096(gpu, dim, p, q):
+    edges, _ = CASES["cliques_walk4100"]
+    _batched_vs_oracle(gpu, _graph(edges), (dim, p, q, 1, 4100, 2, 2, 0.025, 1), 8)

@@ -110,7 +110,7 @@ def test_merge_tie_rule_single_process():
         dist.destroy_process_group()
 
 
-def _n2v_worker(rank, world, port, q, n_nodes=1200):
+def _n2v_worker(rank, world, port, q, n_nodes=1200, dim=32):
     import sys
 
     sys.path.insert(0, ROOT)
@@ -123,28 +123,32 @@ def _n2v_worker(rank, world, port, q, n_nodes=1200):
 
     s, d, _ = planted(n_nodes, 6, 0.08, 0.002, 7)
     g = og.N2vGraph(s, d)
-    emb, st = muninn_amd.pkg.parallel.node2vec_train_distributed(g.off, g.adj, 32, 1.0, 1.0, 2, 20, 3, 3, 0.025, 1, batch_walks=50)
+    emb, st = muninn_amd.pkg.parallel.node2vec_train_distributed(g.off, g.adj, dim, 1.0, 1.0, 2, 20, 3, 3, 0.025, 1, batch_walks=50)
     q.put((rank, emb, st))
     dist.barrier()
     dist.destroy_process_group()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,n_nodes", [(2, 1200), (4, 1206)])
-def test_node2vec_data_parallel_world2_bit_identical_to_one_gpu(gpu, world, n_nodes):
+@pytest.mark.parametrize("world,n_nodes,dim", [pytest.param(2, 1200, 32, id="2-1200"), pytest.param(4, 1206, 32, id="4-1206"),
+                                               pytest.param(2, 1200, 513, id="2-1200-dim513")])
+def test_node2vec_data_parallel_world2_bit_identical_to_one_gpu(gpu, world, n_nodes, dim):
     """Several ranks (gloo exchange, all on the one GPU of the box) train data-parallel — walk slices, samples all-gathered,
     the apply half sharded by destination row (1 206 rows over 4 ranks: a padded last shard) and the row shards all-gathered;
-    every replica must equal the single-process MN_N2V_BATCHED result bit for bit, which itself equals the CPU restatement."""
+    every replica must equal the single-process MN_N2V_BATCHED result bit for bit, which itself equals the CPU restatement.
+    (dim 513: the widest register template, and position records of dim + 1 floats on the exchange.)"""
     from oracle import orc_graph as og
     from oracle.graph_cases import planted
 
     s, d, _ = planted(n_nodes, 6, 0.08, 0.002, 7)
     g = og.N2vGraph(s, d)
-    single, st1 = gpu.node2vec_train(g.off, g.adj, 32, 1.0, 1.0, 2, 20, 3, 3, 0.025, 1, mode=gpu.N2V_BATCHED, batch_walks=50)
+    single, st1 = gpu.node2vec_train(g.off, g.adj, dim, 1.0, 1.0, 2, 20, 3, 3, 0.025, 1, mode=gpu.N2V_BATCHED, batch_walks=50)
+    want, npairs = og.node2vec_train_batched(g, dim, 1.0, 1.0, 2, 20, 3, 3, 0.025, 1, 50)
+    assert np.array_equal(single.view(np.int32), want.view(np.int32)) and st1["pairs"] == npairs
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_n2v_worker, args=(r, world, port, q, n_nodes)) for r in range(world)]
+    procs = [ctx.Process(target=_n2v_worker, args=(r, world, port, q, n_nodes, dim)) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted(_collect(procs, q, world, 300), key=lambda r: r[0])

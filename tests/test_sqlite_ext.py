@@ -281,7 +281,7 @@ def test_node2vec_train_sql_matches_reference_bytes(conn, gpu):
     from oracle.graph_cases import n2v_cases
 
     z = np.load(os.path.join(ROOT, "tests", "golden", "node2vec.npz"))
-    for name in ("cliques16", "karate_pq"):
+    for name in ("cliques16", "karate_pq", "cliques_walk4100", "cliques_d1024"):
         edges, (dim, p, q, nw, wl, win, neg, lr, ep) = n2v_cases()[name]
         conn.execute(f"CREATE TABLE e_{name} (src TEXT, dst TEXT)")
         conn.executemany(f"INSERT INTO e_{name} VALUES (?, ?)", [(str(a), str(b)) for a, b in edges])
