@@ -210,6 +210,9 @@ typedef struct {
     int64_t last_n_overflow; /* queries whose heaps exceeded workspace (must be 0) */
     int64_t last_n_exact_rows; /* f32 rows read for those distances: last_n_dist minus the candidates the fp16 shadow's bound
                                 * rejected (MN_LOWPREC_FILTER; equal to last_n_dist with the filter off) */
+    int64_t last_n_rows_lanes4;  /* ... of which walked by 4 lanes per row, */
+    int64_t last_n_rows_lanes8;  /* by 8 and */
+    int64_t last_n_rows_lanes16; /* by 16 (the filter's survivors in passes with few of them; MN_SURVIVOR_LANES=4|8|16 forces one) */
 } mn_launch_stats;
 int mn_hnsw_last_launch(mn_index *idx, mn_launch_stats *out);
 /* Totals over the batch-synchronous inserts (MN_BUILD_BATCHED / mn_hnsw_build) since the last reset: HIP-event time of

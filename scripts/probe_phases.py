@@ -14,7 +14,7 @@ L = pkg.hnsw.lib()
 for f in ("mn_debug_phase_kernels", "mn_debug_phase_seq"):
     getattr(L, f).argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 def phases(which, reset=True):
-    a = (C.c_ulonglong * 8)()
+    a = (C.c_ulonglong * 16)()  # MN_PHASE_N (mn_beam.hpp)
     assert getattr(L, "mn_debug_phase_" + which)(a, 1 if reset else 0) == 0
     return np.array(list(a), np.float64)
 def show(tag, p, wall_ms, n):

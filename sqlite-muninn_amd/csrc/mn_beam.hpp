@@ -138,8 +138,12 @@ struct CoopCtx {
 
 // -DMN_PHASE_TIMING (scripts/probe_phases.sh builds a separate library with it; never the product): where one search's
 // latency chain goes — per expansion: heap pop, link row + visited probe, distances, heap pushes (s_memrealtime, 100 MHz)
+// Slots: [0..3] those four times, [4] pushes, [5] expansions, [6] link phase (k_insert_seq), [7] pops of the previous runner-up;
+// beam_layer<LP>: [2] is the exact walk alone and [8] the shadow pass (bound + compaction); [9..13] passes in which the filter ran
+// by survivors (0, 1-4, 5-8, 9-16, more), [14] those passes, [15] their candidates
+#define MN_PHASE_N 16
 #ifdef MN_PHASE_TIMING
-static __device__ unsigned long long mn_phase[8];
+static __device__ unsigned long long mn_phase[MN_PHASE_N];
 #define PH_DECL unsigned long long ph_t = __builtin_amdgcn_s_memrealtime()
 #define PH_ADD(w, k)                                                                                                             \
     do {                                                                                                                         \
@@ -156,7 +160,7 @@ static __device__ unsigned long long mn_phase[8];
 
 struct WaveCtx {
 #ifdef MN_PHASE_TIMING
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long ph[MN_PHASE_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     float *tile = nullptr; // LDS staging tile for the coalesced SSE-order loads (k_beam), or null
     const float *q;  // LDS query, zero padded to ld
@@ -174,6 +178,9 @@ struct WaveCtx {
     int lp_on = 0;
     LoQuery lq = {0.0f, 0.0};
     unsigned long long n_skip = 0; // distances decided by the bound alone (counted in n_dist as well)
+    // ... and the survivors' exact walk spreads a row over 8 or 16 lanes when a pass has few of them (sse_rows_spread)
+    int sv_lanes = 0;                        // MN_SURVIVOR_LANES (host): 4 / 8 / 16 = that layout for every pass, 0 = by the pass's rows
+    unsigned long long n_l8 = 0, n_l16 = 0;  // rows walked by 8 / by 16 lanes (every other exact row: by 4)
 };
 DEVI bool getenv_spec_off(const WaveCtx &w) { return (w.no_spec_rows & 1) != 0; }
 
@@ -445,10 +452,36 @@ DEVI void beam_layer(const MnDevIndex &ix, WaveCtx &w, WHeap &cand, WHeap &res, 
                     __builtin_amdgcn_wave_barrier();
                     myslot = lane < ne ? w.scratch[lane] : 0;
                 }
+                PH_ADD(w, 8);
+                PH_CNT(w, 9, ne == 0); // (literal slots: an index computed at run time would put the array in scratch memory)
+                PH_CNT(w, 10, ne >= 1 && ne <= 4);
+                PH_CNT(w, 11, ne >= 5 && ne <= 8);
+                PH_CNT(w, 12, ne >= 9 && ne <= 16);
+                PH_CNT(w, 13, ne > 16);
+                PH_CNT(w, 14, 1);
+                PH_CNT(w, 15, n);
             }
             float d = 0.0f;
-            if (!LP || ne > 0)
-                d = ctx_distance<ORDER, NCH>(ix, w, myslot, ne, lane);
+            // lanes per row of the exact walk (quad loads only): few rows → each over more lanes, its loads in one round trip.
+            // Up to 4 rows: 16 lanes each (one pass, one round trip per 768 floats); up to 8: 8 lanes each (one pass, two round
+            // trips); more: today's 4 lanes (profiles/r06_survivor_walk.txt has the histogram the thresholds were set on)
+            int quads = 1;
+            if (LP && ORDER == MN_ORDER_SSE_V && NCH == 1)
+                quads = w.sv_lanes ? w.sv_lanes >> 2 : (ne <= 4 ? 4 : ne <= 8 ? 2 : 1);
+            if (LP && quads > 1 && ne > 0) {
+                d = rows_distance_spread(ix, w.q, w.qnorm, myslot, ne, lane, quads);
+                if (quads == 4)
+                    w.n_l16 += ne;
+                else
+                    w.n_l8 += ne;
+            } else if (!LP || ne > 0) {
+                // (LP: an opaque copy of the lane id, as in lo_rows_accumulate — what the walk derives from it is then formed per call
+                //  and does not stay in registers round the search loop: k_beam<SSE, 1, LP> 151 -> 110 VGPRs by this line alone)
+                int dl = lane;
+                if (LP)
+                    asm volatile("" : "+v"(dl));
+                d = ctx_distance<ORDER, NCH>(ix, w, myslot, ne, dl);
+            }
             PH_ADD(w, 2);
             // :413-425, in list order.  Once the result set is full an element can only be accepted
             // if it beats the worst AT THAT MOMENT, which never exceeds the worst now: pre-filter.
@@ -496,7 +529,7 @@ DEVI void beam_layer(const MnDevIndex &ix, WaveCtx &w, WHeap &cand, WHeap &res, 
         cand.ovf = 1;
 #ifdef MN_PHASE_TIMING
     if (lane == 0)
-        for (int k = 0; k < 8; k++) {
+        for (int k = 0; k < MN_PHASE_N; k++) {
             atomicAdd(&mn_phase[k], w.ph[k]);
             w.ph[k] = 0;
         }
@@ -798,7 +831,7 @@ DEVI bool beam_layer_regs(const MnDevIndex &ix, WaveCtx &w, WHeap &res, uint2 *p
     }
 #ifdef MN_PHASE_TIMING
     if (lane == 0)
-        for (int k = 0; k < 8; k++) {
+        for (int k = 0; k < MN_PHASE_N; k++) {
             atomicAdd(&mn_phase[k], w.ph[k]);
             w.ph[k] = 0;
         }

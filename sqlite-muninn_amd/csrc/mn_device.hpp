@@ -58,6 +58,7 @@ struct MnDevIndex {
 };
 
 // One launch of the beam-search kernel (search or build flavour).
+#define MN_QC 6 // counters per query of MnSearchArgs::q_counters
 struct MnSearchArgs {
     // queries: either dense host-uploaded vectors [nq][dim] or rows of the index (build)
     const float *queries;
@@ -85,7 +86,8 @@ struct MnSearchArgs {
     uint2 *res_ovf;          // [nq][res_gcap]
     int res_gcap;
     unsigned long long *counters; // [0] n_dist [1] n_expanded [2] overflowed queries [3] distances decided by the fp16 bound alone
-    unsigned long long *q_counters; // or, when not null: [nq][4] the same per query, plain stores (a few queries answered into the
+                                  // [4] [5] exact rows walked by 8 / by 16 lanes (k_beam<LP>, SSE order; [6] [7] spare)
+    unsigned long long *q_counters; // or, when not null: [nq][MN_QC] [0..5] of the same per query, plain stores (a few queries answered into the
                                     // index's pinned host block: no counter memset before the launch, no copy after it)
     int use_tile;                 // SSE order: stage candidate rows through the LDS tile (coalesced loads)
     int lds_bitmap;               // k_beam_coop, search: the layer-0 visited bitmap lives in LDS (small indexes: one query's
@@ -98,6 +100,7 @@ struct MnSearchArgs {
     // lat_tile_off for its share of a distance request (sse_rows_lat_tiled, mn_dist.hpp); 0 rows = none
     int lat_tile_rows;
     unsigned lat_tile_off;
+    int surv_lanes;   // k_beam<LP>: MN_SURVIVOR_LANES — 4, 8 or 16 lanes per surviving row in every pass, 0 = by the pass's rows
     int no_spec_rows; // k_beam_coop: 1 = request a neighbour's row only after the visited probe has answered (MN_SPEC_ROWS=0, A/B runs)
 };
 // dynamic LDS a workgroup of this process may ask for: 64 KB, or what the device grants on request (mn_kernels.hip)

@@ -9,6 +9,10 @@ DEVI int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 DEVI unsigned rflu(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 DEVI float u2f(unsigned u) { return __uint_as_float(u); }
 DEVI unsigned f2u(float f) { return __float_as_uint(f); }
+DEVI double rfl_f64(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return __longlong_as_double((long long)(((unsigned long long)rflu((unsigned)(b >> 32)) << 32) | rflu((unsigned)b)));
+}
 
 // ───────────────────────── distance inner loops ─────────────────────────
 
@@ -261,6 +265,159 @@ DEVI float sse_row(const float *__restrict__ row, const float *q_lds, int dim, i
         sum = __fadd_rn(sum, p);
     }
     return sum;
+}
+
+// ───────────────────────── SSE order, a row spread over Q quads (the fp16 filter's survivors) ─────────────────────────
+// beam_layer<LP> hands the exact walk a few rows per expansion (4.75 on average at 1M x 768, ef 128).  With 4 lanes per row and 12
+// float4 in flight per lane, a 768-float row is four DEPENDENT round trips to memory, each carrying a handful of rows.  Here a row
+// is given to Q = 2 or 4 quads (8 or 16 lanes): a stretch of Q·nb quad blocks is cut into Q contiguous pieces of nb ≤ 12 blocks,
+// quad g loads piece g — every load of the stretch is issued before the first use: ONE round trip for 768 floats at Q = 4 —, and
+// forms its products and the in-quad transposes at once with the other quads (none of that depends on the running sums).  Only
+// the additions are serial, and they stay the reference's chain (src/vec_math.c:81-95): quad 0 adds its 4·nb terms to accumulator
+// j in order, lane j of quad 0 hands the partial sum to lane j of quad 1 (quad_rot), which adds its terms in order, and so on;
+// the last quad's sum goes round to quad 0 for the next stretch.  Same operations in the same order on the same values: same bits.
+// What is left when fewer than Q blocks remain (dim = ld - 1 .. ld - 3: up to 3 blocks, up to 3 chain positions, the scalar tail)
+// is walked by every quad of the row alike, four lanes per row as sse_row does it (sse_row_finish).
+
+// lane i takes the value of lane i - 4 of its group of 4Q lanes, quad 0 that of the group's last quad
+DEVI float quad_rot(float v, int Q) {
+    if (Q == 4) // row_ror:4 — a DPP row is 16 lanes
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, false));
+    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x101F)); // Q == 2: lanes xor 4
+}
+
+// the rest of a row's walk from block t with the running sum s of accumulator j = lane & 3: whole blocks, the chain positions past
+// them, ((s0 + s1) + s2) + s3 and the scalar tail — the end of sse_row, for a walk that was started elsewhere
+template <bool L2>
+DEVI float sse_row_finish(const float *__restrict__ row, const float *q_lds, int dim, int lane, int t, float s) {
+    const int j = lane & 3;
+    const int steps = dim >> 2, blocks = steps >> 2;
+    sse_blocks_quad<L2, 2>(row, q_lds, j, blocks, t, s);
+    sse_blocks_quad<L2, 1>(row, q_lds, j, blocks, t, s);
+    for (int c = blocks << 2; c < steps; c++) {
+        const float b = row[4 * c + j], a = q_lds[4 * c + j];
+        float p;
+        if (L2) {
+            const float d = __fsub_rn(a, b);
+            p = __fmul_rn(d, d);
+        } else {
+            p = __fmul_rn(a, b);
+        }
+        s = __fadd_rn(s, p);
+    }
+    const int g = lane & ~3;
+    const float s0 = __shfl(s, g), s1 = __shfl(s, g + 1), s2 = __shfl(s, g + 2), s3 = __shfl(s, g + 3);
+    float sum = __fadd_rn(__fadd_rn(__fadd_rn(s0, s1), s2), s3);
+    for (int i = steps * 4; i < dim; i++) {
+        const float a = q_lds[i], b = row[i];
+        float p;
+        if (L2) {
+            const float d = __fsub_rn(a, b);
+            p = __fmul_rn(d, d);
+        } else {
+            p = __fmul_rn(a, b);
+        }
+        sum = __fadd_rn(sum, p);
+    }
+    return sum;
+}
+
+#define MN_SPREAD_UB 12 // float4 loads in flight per lane, as MN_SSE_QUAD2 (16 measured slower there)
+// Raw accumulation of n rows (slot per lane, lanes < n valid), Q = 2 or 4 quads per row (wave-uniform); lane i < n gets row i's.
+template <bool L2>
+DEVI float sse_rows_spread(const MnDevIndex &ix, const float *q_lds, int myslot, int n, int lane, int Q) {
+    float mine = 0.0f;
+    int ln = lane; // (an opaque copy, as in lo_rows_accumulate: nothing derived from the lane id stays live outside this call)
+    asm volatile("" : "+v"(ln));
+    const int j = ln & 3, g = (ln >> 2) & (Q - 1);
+    const bool b0 = j & 1, b1 = j & 2;
+    const int sh = Q == 4 ? 4 : 3; // log2 of the lanes per row
+    const int R = 64 >> sh;        // rows per pass
+    const int blocks = ix.dim >> 4;
+    for (int t = 0; t < n; t += R) {
+        const int r = t + (ln >> sh);
+        const int sl = __shfl(myslot, r < n ? r : n - 1);
+        const float *__restrict__ row = ix.vectors + (size_t)sl * ix.ld;
+        float s = 0.0f;
+        int tb = 0;
+        while (blocks - tb >= Q) {
+            const int share = (blocks - tb) / Q;
+            const int nb = share < MN_SPREAD_UB ? share : MN_SPREAD_UB; // (uniform) blocks per quad in this stretch
+            const int off = 16 * (tb + g * nb) + 4 * j;
+            float4 bv[MN_SPREAD_UB];
+#pragma unroll
+            for (int u = 0; u < MN_SPREAD_UB; u++)
+                if (u < nb)
+                    bv[u] = *reinterpret_cast<const float4 *>(row + off + 16 * u);
+            __builtin_amdgcn_sched_barrier(0);
+            float4 an = *reinterpret_cast<const float4 *>(q_lds + off); // (the query's block u + 1 is read while block u is worked on)
+#pragma unroll
+            for (int u = 0; u < MN_SPREAD_UB; u++)
+                if (u < nb) {
+                    const float4 a = an;
+                    if (u + 1 < nb)
+                        an = *reinterpret_cast<const float4 *>(q_lds + off + 16 * (u + 1));
+                    const float4 b = bv[u];
+                    float p0, p1, p2, p3;
+                    if (L2) {
+                        const float d0 = __fsub_rn(a.x, b.x), d1 = __fsub_rn(a.y, b.y), d2 = __fsub_rn(a.z, b.z), d3 = __fsub_rn(a.w, b.w);
+                        p0 = __fmul_rn(d0, d0);
+                        p1 = __fmul_rn(d1, d1);
+                        p2 = __fmul_rn(d2, d2);
+                        p3 = __fmul_rn(d3, d3);
+                    } else {
+                        p0 = __fmul_rn(a.x, b.x);
+                        p1 = __fmul_rn(a.y, b.y);
+                        p2 = __fmul_rn(a.z, b.z);
+                        p3 = __fmul_rn(a.w, b.w);
+                    }
+                    // the 4 x 4 transpose of sse_blocks_quad: accumulator j gets its terms of the block's four chain positions
+                    float r0 = quad_xor1(b0 ? p0 : p1), r1 = quad_xor1(b0 ? p2 : p3);
+                    if (b0) {
+                        p0 = r0;
+                        p2 = r1;
+                    } else {
+                        p1 = r0;
+                        p3 = r1;
+                    }
+                    r0 = quad_xor2(b1 ? p0 : p2);
+                    r1 = quad_xor2(b1 ? p1 : p3);
+                    if (b1) {
+                        p0 = r0;
+                        p1 = r1;
+                    } else {
+                        p2 = r0;
+                        p3 = r1;
+                    }
+                    bv[u] = make_float4(p0, p1, p2, p3);
+                }
+            // the chain: quad 0's terms, then quad 1's on top of quad 0's sum, ...  (the first rotation of a row moves zeros)
+            for (int ph = 0; ph < Q; ph++) {
+                s = quad_rot(s, Q);
+                if (g == ph) {
+#pragma unroll
+                    for (int u = 0; u < MN_SPREAD_UB; u++)
+                        if (u < nb) {
+                            s = __fadd_rn(s, bv[u].x);
+                            s = __fadd_rn(s, bv[u].y);
+                            s = __fadd_rn(s, bv[u].z);
+                            s = __fadd_rn(s, bv[u].w);
+                        }
+                }
+            }
+            tb += Q * nb;
+        }
+        // the sums are with the row's last quad: every quad takes them and finishes the row the same way
+        int lf = ln; // (opaque again: the exchange indices below are formed here, after the walk, not kept in registers through it —
+                     //  that alone is 9 VGPRs of k_beam<LP>)
+        asm volatile("" : "+v"(lf));
+        s = __shfl(s, (lf & ~(4 * Q - 1)) | (4 * (Q - 1)) | (lf & 3));
+        const float v = sse_row_finish<L2>(row, q_lds, ix.dim, lf, tb, s);
+        const float got = __shfl(v, ((lf - t) & (R - 1)) << sh);
+        if (lf >= t && lf < t + R)
+            mine = got;
+    }
+    return mine;
 }
 
 // SSE order with coalesced loads: 16 rows at a time, 128 elements of each per stage.  A wave-instruction
@@ -559,6 +716,17 @@ DEVI float rows_distance(const MnDevIndex &ix, const float *q_lds, float qnorm, 
     if (ix.metric == 2)
         return -dot; // src/vec_math.c:142
     float nb = (lane < n) ? ix.norms[myslot] : 1.0f;
+    return cosine_finish(dot, qnorm, nb);
+}
+
+// rows_distance<MN_ORDER_SSE_V, 1> with the rows spread over Q = 2 or 4 quads each (sse_rows_spread): the same bits
+DEVI float rows_distance_spread(const MnDevIndex &ix, const float *q_lds, float qnorm, int myslot, int n, int lane, int Q) {
+    if (ix.metric == 0)
+        return sse_rows_spread<true>(ix, q_lds, myslot, n, lane, Q);
+    const float dot = sse_rows_spread<false>(ix, q_lds, myslot, n, lane, Q);
+    if (ix.metric == 2)
+        return -dot; // src/vec_math.c:142
+    const float nb = (lane < n) ? ix.norms[myslot] : 1.0f;
     return cosine_finish(dot, qnorm, nb);
 }
 

@@ -180,7 +180,7 @@ struct mn_index {
     DevBuf<float> sh_gd, sh_ld;
     long long last_spec_searched = 0; // searches the last speculative build ran (≥ nodes inserted)
     bool broken = false; // an insert failed after its kernels had begun to rewrite link rows: nothing can be trusted
-    mn_launch_stats last = {0, 0, 0, 0, 0};
+    mn_launch_stats last = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // ───────────────────────── small host helpers ─────────────────────────
@@ -800,7 +800,7 @@ static int reserve_search_ws(mn_index *x, int64_t nq, int ef) {
     if (x->ws_bm0.reserve((size_t)nq * bm0_words, false, st)) return -1;
     if (x->ws_cand.reserve((size_t)nq * (16 * ef + 1024), false, st)) return -1;
     if (x->ws_res.reserve((size_t)nq * (ef > MN_RES_LDS ? ef : 8), false, st)) return -1;
-    if (x->ws_counters.reserve(4, false, st)) return -1;
+    if (x->ws_counters.reserve(8, false, st)) return -1; // MnSearchArgs::counters
     return 0;
 }
 
@@ -819,7 +819,7 @@ static int prepare_search_ws(mn_index *x, int64_t nq, int ef, MnSearchArgs &a, b
     if (!a.lds_bitmap)
         HIPCHK(hipMemsetAsync(x->ws_bm0.p, 0, (size_t)nq * a.bm0_words * sizeof(unsigned), st));
     if (zero_counters)
-        HIPCHK(hipMemsetAsync(x->ws_counters.p, 0, 4 * sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(x->ws_counters.p, 0, 8 * sizeof(unsigned long long), st));
     a.bitmap0 = x->ws_bm0.p;
     a.cand_ovf = x->ws_cand.p;
     a.res_ovf = x->ws_res.p;
@@ -844,7 +844,7 @@ static int prepare_search_ws(mn_index *x, int64_t nq, int ef, MnSearchArgs &a, b
 }
 
 static int fetch_counters(mn_index *x) {
-    unsigned long long c[4];
+    unsigned long long c[8];
     if (!x->ws_counters.p) // nothing launched yet
         return 0;
     HIPCHK(hipMemcpyAsync(c, x->ws_counters.p, sizeof(c), hipMemcpyDeviceToHost, x->stream));
@@ -856,6 +856,9 @@ static int fetch_counters(mn_index *x) {
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
     x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
+    x->last.last_n_rows_lanes8 = (int64_t)c[4];
+    x->last.last_n_rows_lanes16 = (int64_t)c[5];
+    x->last.last_n_rows_lanes4 = x->last.last_n_exact_rows - (int64_t)(c[4] + c[5]);
     return 0;
 }
 
@@ -904,7 +907,7 @@ static int search_batch_dev_impl(mn_index *x, const float *d_queries, int64_t nq
                 (void)hipEventRecord(x->ev1, st);
             return -1;
         }
-        a.q_counters = q_counters ? q_counters + (size_t)q0 * 4 : nullptr;
+        a.q_counters = q_counters ? q_counters + (size_t)q0 * MN_QC : nullptr;
         a.queries = d_queries + (size_t)q0 * x->dim;
         a.nq = m;
         a.k = k;
@@ -972,6 +975,8 @@ static int counters_from(mn_index *x, const unsigned long long *c) {
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
     x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
+    x->last.last_n_rows_lanes4 = x->last.last_n_exact_rows; // (the few-queries kernels walk every row with 4 lanes)
+    x->last.last_n_rows_lanes8 = x->last.last_n_rows_lanes16 = 0;
     return 0;
 }
 
@@ -983,7 +988,7 @@ static int search_small(mn_index *x, const float *queries, int64_t nq, int k, in
     const size_t qb = (size_t)nq * x->dim * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t), db = (size_t)nq * k * sizeof(float);
     const size_t cb = ((size_t)nq * sizeof(int) + 7) & ~(size_t)7;
     const size_t o_ids = (qb + 15) & ~(size_t)15, o_d = o_ids + ib, o_c = (o_d + db + 7) & ~(size_t)7, o_cnt = o_c + cb;
-    const size_t need = o_cnt + (size_t)nq * 4 * sizeof(unsigned long long);
+    const size_t need = o_cnt + (size_t)nq * MN_QC * sizeof(unsigned long long);
     if (push_links(x) || sync_meta(x)) // (before the block is written: a pending single-slot upload stages through it too)
         return -1;
     if (!pin_reserve(x, need)) {
@@ -1002,13 +1007,14 @@ static int search_small(mn_index *x, const float *queries, int64_t nq, int k, in
     memcpy(out_dists, x->pin + o_d, db);
     memcpy(out_counts, x->pin + o_c, (size_t)nq * sizeof(int));
     if (launched) {
-        unsigned long long tot[4] = {0, 0, 0, 0};
+        unsigned long long tot[MN_QC] = {0, 0, 0, 0, 0, 0};
         for (int64_t q = 0; q < nq; q++)
-            for (int i = 0; i < 3; i++)
-                tot[i] += qc[q * 4 + i];
-        for (int64_t q = 0; q < nq; q++)
-            tot[3] += qc[q * 4 + 3];
+            for (int i = 0; i < MN_QC; i++)
+                tot[i] += qc[q * MN_QC + i];
         x->last.last_n_exact_rows = (int64_t)(tot[0] - tot[3]);
+        x->last.last_n_rows_lanes8 = (int64_t)tot[4];
+        x->last.last_n_rows_lanes16 = (int64_t)tot[5];
+        x->last.last_n_rows_lanes4 = x->last.last_n_exact_rows - (int64_t)(tot[4] + tot[5]);
         x->last.last_n_dist = (int64_t)tot[0];
         x->last.last_n_expanded = (int64_t)tot[1];
         x->last.last_n_overflow = (int64_t)tot[2];

@@ -258,6 +258,11 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
     if (LP) {
         w.lq = lo_query(ix.metric == 1 ? w.qnorm : lds_self_norm<ORDER>(q, ix.dim, ix.ld, lane), ix.ld);
         w.lp_on = w.lq.qn_hi <= 1.0e300;
+        // (the same value in every lane, but out of a __shfl: kept in scalar registers from here on)
+        w.lq.qs_lo = rfl_f64(w.lq.qs_lo);
+        w.lq.qn_hi = rfl_f64(w.lq.qn_hi);
+        w.qnorm = u2f(rflu(f2u(w.qnorm)));
+        w.sv_lanes = a.surv_lanes;
     }
     if (BUILD && a.readlog) {
         w.rlog = a.readlog + (size_t)qi * a.readcap * MN_RLOG_INTS;
@@ -342,10 +347,12 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
             a.nread[qi] = LAT ? w.nr : a.readcap + 1; // > readcap: the log is incomplete and the commit step must not trust it
                                                       // (only the latency kernel's searches keep a log)
         if (a.q_counters) {
-            a.q_counters[(size_t)qi * 4 + 0] = w.n_dist;
-            a.q_counters[(size_t)qi * 4 + 1] = w.n_exp;
-            a.q_counters[(size_t)qi * 4 + 2] = (cand.ovf || res.ovf) ? 1ull : 0ull;
-            a.q_counters[(size_t)qi * 4 + 3] = w.n_skip;
+            a.q_counters[(size_t)qi * MN_QC + 0] = w.n_dist;
+            a.q_counters[(size_t)qi * MN_QC + 1] = w.n_exp;
+            a.q_counters[(size_t)qi * MN_QC + 2] = (cand.ovf || res.ovf) ? 1ull : 0ull;
+            a.q_counters[(size_t)qi * MN_QC + 3] = w.n_skip;
+            a.q_counters[(size_t)qi * MN_QC + 4] = w.n_l8;
+            a.q_counters[(size_t)qi * MN_QC + 5] = w.n_l16;
         } else {
             atomicAdd(&a.counters[0], w.n_dist);
             atomicAdd(&a.counters[1], w.n_exp);
@@ -353,6 +360,10 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
                 atomicAdd(&a.counters[2], 1ull);
             if (LP && w.n_skip)
                 atomicAdd(&a.counters[3], w.n_skip);
+            if (LP && w.n_l8)
+                atomicAdd(&a.counters[4], w.n_l8);
+            if (LP && w.n_l16)
+                atomicAdd(&a.counters[5], w.n_l16);
         }
     }
 }
@@ -511,10 +522,16 @@ static void launch_beam(const MnDevIndex &ix, const MnSearchArgs &a, bool build,
     // that one process can A/B the two)
     const char *lp = getenv("MN_LOWPREC_FILTER");
     if (!build && ix.vec_lo && ix.lo_meta && !(lp && atoi(lp) == 0)) {
+        // the survivors' exact walk: MN_SURVIVOR_LANES=4|8|16 forces one layout for every pass (read per launch), anything else =
+        // by the pass's rows (beam_layer<LP>)
+        MnSearchArgs al = a;
+        const char *sv = getenv("MN_SURVIVOR_LANES");
+        const int svl = sv ? atoi(sv) : 0;
+        al.surv_lanes = (svl == 4 || svl == 8 || svl == 16) ? svl : 0;
         if (wide)
-            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, true, true>), grid, block, lds, st, ix, a);
+            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, true, true>), grid, block, lds, st, ix, al);
         else
-            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, false, true>), grid, block, lds, st, ix, a);
+            hipLaunchKernelGGL((k_beam<ORDER, NCH, false, false, true>), grid, block, lds, st, ix, al);
         return;
     }
     if (wide) {
@@ -662,10 +679,10 @@ void mn_launch_merge_topk(const long long *g_ids, const float *g_dists, const in
 
 #ifdef MN_PHASE_TIMING
 extern "C" int mn_debug_phase_kernels(unsigned long long *out, int reset) { // probe builds only (scripts/probe_phases.sh)
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mn_phase), 8 * sizeof(unsigned long long)) != hipSuccess)
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mn_phase), MN_PHASE_N * sizeof(unsigned long long)) != hipSuccess) // out: MN_PHASE_N slots
         return -1;
     if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long z[MN_PHASE_N] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(mn_phase), z, sizeof(z)) != hipSuccess)
             return -1;
     }

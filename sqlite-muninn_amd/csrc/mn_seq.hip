@@ -491,10 +491,10 @@ void mn_launch_insert_seq(const MnDevIndex &ix, const int *d_slots, int n, int e
 
 #ifdef MN_PHASE_TIMING
 extern "C" int mn_debug_phase_seq(unsigned long long *out, int reset) { // probe builds only (scripts/probe_phases.sh)
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mn_phase), 8 * sizeof(unsigned long long)) != hipSuccess)
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mn_phase), MN_PHASE_N * sizeof(unsigned long long)) != hipSuccess) // out: MN_PHASE_N slots
         return -1;
     if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long z[MN_PHASE_N] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(mn_phase), z, sizeof(z)) != hipSuccess)
             return -1;
     }

@@ -33,7 +33,8 @@ class _Result(C.Structure):
 
 class LaunchStats(C.Structure):
     _fields_ = [("last_kernel_ms", C.c_double), ("last_n_dist", C.c_int64), ("last_n_expanded", C.c_int64),
-                ("last_n_overflow", C.c_int64), ("last_n_exact_rows", C.c_int64)]
+                ("last_n_overflow", C.c_int64), ("last_n_exact_rows", C.c_int64),
+                ("last_n_rows_lanes4", C.c_int64), ("last_n_rows_lanes8", C.c_int64), ("last_n_rows_lanes16", C.c_int64)]
 
 
 class BuildStats(C.Structure):
