@@ -386,13 +386,16 @@ def bench_leiden(pkg, args):
 # "muninn / erdos-renyi-20", query time through SQL): ms by node count
 PUBLISHED_MS = {"pagerank": {1000: 44.423, 5000: 947.58, 10000: 3756.147, 50000: 299032.738},
                 "components": {1000: 42.074, 5000: 948.109, 10000: 3747.119, 50000: 143310.545},
-                "betweenness": {1000: 130.058, 5000: 3496.249, 10000: 16663.205}}
+                "betweenness": {1000: 130.058, 5000: 3496.249, 10000: 16663.205},
+                "closeness": {1000: 133.045, 5000: 3280.86, 10000: 15511.165}}  # graph_query_time_closeness.json
 TVF_SQL = {"pagerank": "SELECT node, rank FROM graph_pagerank WHERE edge_table = 'bench_edges' AND src_col = 'src' AND dst_col = 'dst' "
                        "AND damping = 0.85 AND iterations = 100",
            "components": "SELECT node, component_id FROM graph_components WHERE edge_table = 'bench_edges' AND src_col = 'src' "
                          "AND dst_col = 'dst'",
            "betweenness": "SELECT node, centrality FROM graph_node_betweenness WHERE edge_table = 'bench_edges' AND src_col = 'src' "
-                          "AND dst_col = 'dst' AND direction = 'both'"}
+                          "AND dst_col = 'dst' AND direction = 'both'",
+           "closeness": "SELECT node, centrality FROM graph_closeness WHERE edge_table = 'bench_edges' AND src_col = 'src' "
+                        "AND dst_col = 'dst' AND direction = 'both'"}
 
 
 def er_rows(n, avg_degree, seed=42):
@@ -470,6 +473,24 @@ def bench_tvf(pkg, args, what):
         big = {"nodes": n_big, "edge_rows": int(E), "device_ms": dev_ms, "wall_ms": wall * 1e3,
                "sources_per_s": n_big / (dev_ms * 1e-3)}
         unit, value = "sources/s", n_big / wall
+    elif what == "closeness":
+        n_big = args.tvf_betweenness_nodes
+        bs, bd = er_rows(n_big, 20)
+        g = pkg.graph.graph_from_edges(n_big, bs[0::2], bd[0::2], device=dev)  # (each undirected edge once: out + in lists)
+        g.closeness("both")
+        t0 = time.perf_counter()
+        cc, dev_ms = g.closeness("both")
+        wall = time.perf_counter() - t0
+        g.close()
+        E = len(bs)
+        # Bit-parallel BFS, 64 sources per word: every adjacency entry carries every batch's frontier word at least once
+        # (8 B of seen[] read + 8 B OR-ed into next[]), and every (node, batch) keeps three words that are written at least
+        # once: n / 64 batches x (E_dir x 16 B + n x 24 B).  Independent of the number of levels, so a lower bound.
+        alg = float((n_big + 63) // 64) * (E * 16 + n_big * 24)
+        big = {"nodes": n_big, "edge_rows": int(E), "device_ms": dev_ms, "wall_ms": wall * 1e3,
+               "sources_per_s": n_big / (dev_ms * 1e-3), "zero_closeness_nodes": int((cc == 0).sum()),
+               "algorithmic_bytes": "n/64 batches x (adjacency entries x 16 B + n x 24 B): each entry moves each batch's word once"}
+        unit, value = "sources/s", n_big / wall
     else:
         n_big = args.tvf_nodes
         bs, bd = er_rows(n_big, 20)
@@ -516,11 +537,11 @@ def bench_tvf(pkg, args, what):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="both", choices=["node2vec", "leiden", "both", "pagerank", "components", "betweenness", "tvf"],
-                    help="both = node2vec + leiden (configs 4 and 5); tvf = pagerank + components + betweenness (SURVEY 8 f-4)")
+    ap.add_argument("--workload", default="both", choices=["node2vec", "leiden", "both", "pagerank", "components", "betweenness", "closeness", "tvf"],
+                    help="both = node2vec + leiden (configs 4 and 5); tvf = pagerank + components + betweenness + closeness (SURVEY 8 f-4)")
     ap.add_argument("--tvf-published-nodes", type=int, default=10_000, help="f-4: node count of the reference's published point")
     ap.add_argument("--tvf-nodes", type=int, default=1_000_000, help="f-4: pagerank / components through the C-ABI")
-    ap.add_argument("--tvf-betweenness-nodes", type=int, default=20_000)
+    ap.add_argument("--tvf-betweenness-nodes", type=int, default=20_000, help="f-4: betweenness / closeness through the C-ABI")
     ap.add_argument("--no-ref-sql", action="store_true", help="f-4: skip the compiled reference's SQL run")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
@@ -556,7 +577,7 @@ def main():
             line = fn(pkg, args)
             if line is not None:  # rank 0
                 print(json.dumps(line), flush=True)
-    for name in ("pagerank", "components", "betweenness"):
+    for name in ("pagerank", "components", "betweenness", "closeness"):
         if args.workload in (name, "tvf"):
             line = bench_tvf(pkg, args, name)
             if line is not None:

@@ -282,10 +282,24 @@ int mn_graph_leiden_stats(mn_graph *g, mn_leiden_stats *out);
  * The graph must have been created with the lists the direction traverses (out for 1, in for 2, both for 0), as
  * graph_data_load fills them (src/graph_load.c:144-250).  Bit-identical to the reference.  0 / -1. */
 int mn_graph_betweenness(mn_graph *g, int direction, int auto_approx, int normalized, double *cb_out, double *eb_out);
-double mn_graph_last_ms(mn_graph *g); /* device time of the last betweenness call */
+double mn_graph_last_ms(mn_graph *g); /* device time of the last betweenness / closeness call */
 /* GraphData.out as CSR on the host (off[n+1], tgt[mn_graph_out_edge_count]) — the order graph_edge_betweenness emits rows in */
 long long mn_graph_out_edge_count(mn_graph *g);
 int mn_graph_out_lists(mn_graph *g, int *off, int *tgt);
+
+/* clo_filter's per-source loop (src/graph_centrality.c:1396-1434): out[n] = closeness of every node = reachable / sum of
+ * distances, times reachable / (n - 1) when normalized.  direction 0 = both, 1 = forward, 2 = reverse, with
+ * mn_graph_betweenness's meaning and the same requirement on which lists the graph holds.  Unweighted graphs run a
+ * bit-parallel multi-source BFS (64 sources per word: the sum of integer distances is exact in any order), weighted ones
+ * the reference's Dijkstra one lane per source.  Sources go through in chunks under a scratch budget: half of the free
+ * device memory, or MN_CLOSENESS_SCRATCH_MB MiB (fractions allowed) — 24 bytes per node per batch of 64 sources when
+ * unweighted; 12 bytes per node + 16 bytes per (traversed edge + 2) per source when weighted.  n > 2^26 is refused.
+ * Bit-identical to the reference; sets mn_graph_last_ms.  0 / -1. */
+int mn_graph_closeness(mn_graph *g, int direction, int normalized, double *out);
+/* deg_filter's loop (:667-680): sums of out-/in-list weights in list order (1.0 per entry where the graph has no weights; a
+ * list the graph does not hold contributes 0), degree = in + out, centrality = degree, or degree / (n - 1) when
+ * normalized && n > 1.  Any output pointer may be NULL.  0 / -1. */
+int mn_graph_degree(mn_graph *g, int normalized, double *in_deg, double *out_deg, double *degree, double *centrality);
 
 /* ---- node2vec.c replacements (a14-a17) ---- */
 typedef struct {

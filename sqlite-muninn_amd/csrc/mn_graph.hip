@@ -2241,3 +2241,401 @@ extern "C" int mn_graph_out_lists(mn_graph *g, int *off, int *tgt) try {
         GCHK(hipMemcpy(tgt, g->tgt_out, (size_t)g->e_out * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 } MN_GUARD_END(gset_err, MN_NOTHING, -1)
+
+// ───────────────────────── closeness and degree (src/graph_centrality.c:1316-1455 and :591-686) ─────────────────────────
+// clo_filter runs one shortest-path pass per node and keeps of it only the distances: closeness[s] = reachable / sum_dist,
+// times reachable / (N - 1) when normalized (Wasserman-Faust).
+//
+// Unweighted graphs: every distance of sssp_bfs is an integer-valued double, so sum_dist is a sum of integers below 2^53 —
+// exact in ANY order, and equal to  sum over levels of  level x (nodes first reached at that level).  The traversal order
+// therefore does not enter the result and the passes need not be replayed one lane per source: the device runs a
+// level-synchronous BIT-PARALLEL multi-source BFS.  A 64-bit word holds one bit per source of a batch of 64 sources; per node
+// and batch there are the words seen / frontier / next, laid out [node][batch] so that the 64 lanes of a wavefront working
+// on one node touch 64 adjacent words.
+//   k_clo_expand   one wavefront per (node v, 64 batches): the neighbour list of v is read once, wave-uniformly, and
+//                  frontier[v] & ~seen[w] is OR-ed into next[w] — the atomics of one neighbour land in one 512-byte run
+//   k_clo_update   one workgroup per 64 nodes x 64 batches: new = next & ~seen, seen |= new, frontier = new, next = 0 with
+//                  lanes over batches; the new words go through LDS and are read back with lanes over NODES, so that 64
+//                  ballots + popcounts give, per source of the batch, how many of the 64 nodes it just reached: lane `bit`
+//                  adds that count to reachable[source] and count x level to sum_dist[source] (two 64-bit atomics per
+//                  (64 nodes, source) that gained anything, none per (node, bit))
+// Sources are processed in chunks of batches under a scratch budget (24 bytes per node per batch); a level ends when the
+// update kernel saw no new bit in any batch.
+//
+// Weighted graphs have no such freedom (the 1e-10 slack of sssp_dijkstra and f64 sums of non-integers): ONE LANE PER SOURCE
+// replays sssp_dijkstra with dpq_push / dpq_pop verbatim, as k_brandes_sources does, but without sigma, predecessor lists
+// and stack — the distances depend on none of them — then sums dist[] in index order and applies the same two f64 operations.
+typedef unsigned long long clo_word;
+
+DEVI double clo_value(long long reachable, double sum_dist, int normalized, int N) { // :1426-1433
+    if (!(reachable > 0 && sum_dist > 0))
+        return 0.0;
+    double cc = (double)reachable / sum_dist;
+    if (normalized && N > 1)
+        cc *= (double)reachable / (double)(N - 1);
+    return cc;
+}
+
+// the chunk holds the batches b0 .. b0 + B - 1; source s = 64 * batch + bit starts at node s
+__global__ void __launch_bounds__(256) k_clo_init(int N, int B, long long b0, clo_word *seen, clo_word *frontier, clo_word *next) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)N * B)
+        return;
+    const int v = (int)(i / B), b = (int)(i % B);
+    const clo_word w = (long long)(v >> 6) == b0 + b ? (clo_word)1 << (v & 63) : 0;
+    seen[i] = w;
+    frontier[i] = w;
+    next[i] = 0;
+}
+
+__global__ void __launch_bounds__(256) k_clo_expand(DevGraph g, int use_out, int use_in, int B, const clo_word *seen,
+                                                    const clo_word *frontier, clo_word *next) {
+    const int b = blockIdx.y * 64 + (threadIdx.x & 63);
+    for (int vv = blockIdx.x * 4 + (threadIdx.x >> 6); vv < g.n; vv += gridDim.x * 4) { // (vv is the same in all 64 lanes)
+        const int v = __builtin_amdgcn_readfirstlane(vv);
+        const clo_word f = b < B ? frontier[(size_t)v * B + b] : 0;
+        if (__ballot(f != 0) == 0)
+            continue;
+        for (int pass = 0; pass < 2; pass++) { // out[v], then in[v], as sssp_bfs (:286-289); the order does not matter here
+            if (pass == 0 ? !use_out : !use_in)
+                continue;
+            const int *off = pass ? g.off_in : g.off_out, *tgt = pass ? g.tgt_in : g.tgt_out;
+            const int e1 = off[v + 1];
+            for (int e = off[v]; e < e1; e++) {
+                const int w = tgt[e];
+                if (f != 0) {
+                    const size_t i = (size_t)w * B + b;
+                    const clo_word m = f & ~seen[i];
+                    if (m != 0)
+                        atomicOr(&next[i], m);
+                }
+            }
+        }
+    }
+}
+
+#define CLO_TILE_PAD 65 // words per LDS row: the column reads of the counting pass then spread over the banks
+__global__ void __launch_bounds__(256) k_clo_update(int N, int B, long long b0, long long level, clo_word *seen, clo_word *frontier,
+                                                    clo_word *next, unsigned long long *reachable, unsigned long long *sum_dist,
+                                                    int *any_new) {
+    __shared__ clo_word tile[64 * CLO_TILE_PAD];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int v0 = blockIdx.x * 64, bb = blockIdx.y * 64;
+    const int b = bb + lane;
+    int any = 0;
+    for (int r = wv; r < 64; r += 4) { // lanes over batches
+        const int v = v0 + r;
+        clo_word nw = 0;
+        if (v < N && b < B) {
+            const size_t i = (size_t)v * B + b;
+            const clo_word nx = next[i], sn = seen[i];
+            nw = nx & ~sn;
+            if (nw != 0)
+                seen[i] = sn | nw;
+            frontier[i] = nw;
+            if (nx != 0)
+                next[i] = 0;
+        }
+        tile[r * CLO_TILE_PAD + lane] = nw;
+        any |= nw != 0;
+    }
+    if (!__syncthreads_or(any))
+        return;
+    if (threadIdx.x == 0)
+        *any_new = 1;
+    for (int c = wv * 16; c < wv * 16 + 16; c++) { // lanes over nodes: one batch per step
+        if (bb + c >= B)
+            break;
+        const clo_word x = tile[lane * CLO_TILE_PAD + c];
+        if (__ballot(x != 0) == 0)
+            continue;
+        unsigned long long cnt = 0;
+#pragma unroll
+        for (int bit = 0; bit < 64; bit++) {
+            const unsigned long long m = __ballot((x >> bit) & 1);
+            if (lane == bit)
+                cnt = (unsigned long long)__popcll(m);
+        }
+        if (cnt != 0) {
+            const size_t s = (size_t)(b0 + bb + c) * 64 + lane;
+            atomicAdd(&reachable[s], cnt);
+            atomicAdd(&sum_dist[s], cnt * (unsigned long long)level);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_clo_finish(int N, int normalized, const unsigned long long *reachable,
+                                                    const unsigned long long *sum_dist, double *cc) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < N)
+        cc[s] = clo_value((long long)reachable[s], (double)sum_dist[s], normalized, N);
+}
+
+struct CloArgs {
+    DevGraph g;
+    int use_out, use_in, normalized;
+    int s0, n_src;       // this chunk's sources are s0 .. s0 + n_src - 1
+    long long heap_cap;  // entries per source
+    double *dist;        // [n_src][N]
+    int *settled;        // [n_src][N]
+    BrDpq *heap;         // [n_src][heap_cap]
+    double *cc;          // [N]
+    int *overflow;
+};
+
+__global__ void __launch_bounds__(64) k_clo_dijkstra(CloArgs a) {
+    const int si = blockIdx.x * blockDim.x + threadIdx.x;
+    if (si >= a.n_src)
+        return;
+    const int N = a.g.n, src = a.s0 + si;
+    double *dist = a.dist + (size_t)si * N;
+    int *settled = a.settled + (size_t)si * N;
+    for (int i = 0; i < N; i++) {
+        dist[i] = -1.0;
+        settled[i] = 0;
+    }
+    dist[src] = 0.0;
+    // sssp_dijkstra, :321-378, with dpq_push / dpq_pop (:158-212) verbatim
+    BrDpq *h = a.heap + (size_t)si * a.heap_cap;
+    int hs = 0;
+    h[hs].node = src;
+    h[hs].dist = 0.0;
+    hs++;
+    while (hs > 0) {
+        const BrDpq top = h[0];
+        hs--;
+        if (hs > 0) {
+            h[0] = h[hs];
+            int i = 0;
+            for (;;) {
+                const int left = 2 * i + 1, right = 2 * i + 2;
+                int smallest = i;
+                if (left < hs && h[left].dist < h[smallest].dist)
+                    smallest = left;
+                if (right < hs && h[right].dist < h[smallest].dist)
+                    smallest = right;
+                if (smallest == i)
+                    break;
+                const BrDpq t = h[i];
+                h[i] = h[smallest];
+                h[smallest] = t;
+                i = smallest;
+            }
+        }
+        const int v = top.node;
+        if (settled[v])
+            continue;
+        settled[v] = 1;
+        for (int pass = 0; pass < 2; pass++) {
+            if (pass == 0 ? !a.use_out : !a.use_in)
+                continue;
+            const int *off = pass ? a.g.off_in : a.g.off_out, *tgt = pass ? a.g.tgt_in : a.g.tgt_out;
+            const double *wt = pass ? a.g.w_in : a.g.w_out;
+            for (int e = off[v]; e < off[v + 1]; e++) {
+                const int w = tgt[e];
+                const double nd = dist[v] + (wt ? wt[e] : 1.0);
+                if (dist[w] < 0 || nd < dist[w] - 1e-10) {
+                    dist[w] = nd;
+                    if (hs >= a.heap_cap) {
+                        *a.overflow = 1;
+                        return;
+                    }
+                    int i = hs++;
+                    h[i].node = w;
+                    h[i].dist = nd;
+                    while (i > 0) {
+                        const int parent = (i - 1) / 2;
+                        if (h[parent].dist <= h[i].dist)
+                            break;
+                        const BrDpq t = h[parent];
+                        h[parent] = h[i];
+                        h[i] = t;
+                        i = parent;
+                    }
+                }
+            }
+        }
+    }
+    double sum_dist = 0.0; // :1417-1424
+    int reachable = 0;
+    for (int i = 0; i < N; i++)
+        if (i != src && dist[i] >= 0) {
+            sum_dist += dist[i];
+            reachable++;
+        }
+    a.cc[src] = clo_value(reachable, sum_dist, a.normalized, N);
+}
+
+// half of the free device memory unless MN_CLOSENESS_SCRATCH_MB (a decimal number of MiB, fractions allowed) says otherwise
+static size_t clo_budget() {
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        budget = std::max<size_t>((size_t)256 << 20, free_b / 2);
+    if (const char *e = getenv("MN_CLOSENESS_SCRATCH_MB")) {
+        const double mb = strtod(e, nullptr);
+        budget = mb > 0 ? (size_t)(mb * 1048576.0) : 0;
+    }
+    return budget;
+}
+
+extern "C" int mn_graph_closeness(mn_graph *g, int direction, int normalized, double *out) try {
+    GCHK(hipSetDevice(g->device));
+    const int N = g->n;
+    if (N == 0)
+        return 0;
+    if (direction < 0 || direction > 2) {
+        gset_err("mn_graph_closeness: direction must be 0 (both), 1 (forward) or 2 (reverse)");
+        return -1;
+    }
+    if (N > (1 << 26)) { // (N - 1)^2 bounds sum_dist: past this it leaves the range in which every integer is a double
+        gset_err("mn_graph_closeness: more than 2^26 nodes (N = %d)", N);
+        return -1;
+    }
+    const int use_out = direction != 2, use_in = direction == 2 || direction == 0; // :278-279
+    hipStream_t st = g->stream;
+    struct Scr {
+        std::vector<void *> p;
+        ~Scr() {
+            for (void *q : p)
+                (void)hipFree(q);
+        }
+        void *get(size_t bytes) {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess)
+                return nullptr;
+            p.push_back(q);
+            return q;
+        }
+    } scr;
+    const DevGraph dg = {N, g->off_out, g->tgt_out, g->w_out, g->off_in, g->tgt_in, g->w_in};
+    const size_t budget = clo_budget();
+    double *d_cc = (double *)scr.get((size_t)N * sizeof(double));
+    int *d_flag = (int *)scr.get(sizeof(int));
+    int ovf = 0;
+    if (!g->weighted) {
+        const long long nb_total = ((long long)N + 63) / 64;
+        const size_t per_batch = (size_t)N * 3 * sizeof(clo_word);
+        // (at most 2^30 words per array: every launch below then stays inside the 2^32 threads a grid may have)
+        const int B = (int)std::max<size_t>(1, std::min<size_t>({(size_t)nb_total, budget / per_batch, ((size_t)1 << 30) / (size_t)N}));
+        clo_word *seen = (clo_word *)scr.get((size_t)N * B * sizeof(clo_word));
+        clo_word *frontier = (clo_word *)scr.get((size_t)N * B * sizeof(clo_word));
+        clo_word *next = (clo_word *)scr.get((size_t)N * B * sizeof(clo_word));
+        unsigned long long *reach = (unsigned long long *)scr.get((size_t)nb_total * 64 * sizeof(unsigned long long));
+        unsigned long long *sum = (unsigned long long *)scr.get((size_t)nb_total * 64 * sizeof(unsigned long long));
+        if (!d_cc || !d_flag || !seen || !frontier || !next || !reach || !sum) {
+            gset_err("mn_graph_closeness: out of device memory (N = %d, %d batches of 64 sources at once)", N, B);
+            return -1;
+        }
+        GCHK(hipMemsetAsync(reach, 0, (size_t)nb_total * 64 * sizeof(unsigned long long), st));
+        GCHK(hipMemsetAsync(sum, 0, (size_t)nb_total * 64 * sizeof(unsigned long long), st));
+        GCHK(hipEventRecord(g->ev0, st));
+        for (long long b0 = 0; b0 < nb_total; b0 += B) {
+            const int Bc = (int)std::min<long long>(B, nb_total - b0);
+            const size_t words = (size_t)N * Bc;
+            hipLaunchKernelGGL(k_clo_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, N, Bc, b0, seen, frontier, next);
+            const dim3 grid_e(std::min((N + 3) / 4, 1 << 16), (Bc + 63) / 64), grid_u((N + 63) / 64, (Bc + 63) / 64);
+            for (long long level = 1; level <= N; level++) { // (a level past N - 1 cannot add a bit)
+                GCHK(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+                hipLaunchKernelGGL(k_clo_expand, grid_e, dim3(256), 0, st, dg, use_out, use_in, Bc, seen, frontier, next);
+                hipLaunchKernelGGL(k_clo_update, grid_u, dim3(256), 0, st, N, Bc, b0, level, seen, frontier, next, reach, sum, d_flag);
+                int any_new = 0;
+                GCHK(hipMemcpyAsync(&any_new, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+                GCHK(hipStreamSynchronize(st));
+                if (!any_new)
+                    break;
+            }
+        }
+        hipLaunchKernelGGL(k_clo_finish, dim3((N + 255) / 256), dim3(256), 0, st, N, normalized ? 1 : 0, reach, sum, d_cc);
+    } else {
+        const long long e_trav = (use_out ? g->e_out : 0) + (use_in ? g->e_in : 0);
+        CloArgs a;
+        memset(&a, 0, sizeof(a));
+        a.g = dg;
+        a.use_out = use_out;
+        a.use_in = use_in;
+        a.normalized = normalized ? 1 : 0;
+        a.heap_cap = e_trav + 2;
+        const size_t per_src = (size_t)N * (sizeof(double) + sizeof(int)) + (size_t)a.heap_cap * sizeof(BrDpq);
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)N, budget / per_src));
+        a.dist = (double *)scr.get((size_t)chunk * N * sizeof(double));
+        a.settled = (int *)scr.get((size_t)chunk * N * sizeof(int));
+        a.heap = (BrDpq *)scr.get((size_t)chunk * a.heap_cap * sizeof(BrDpq));
+        a.cc = d_cc;
+        a.overflow = d_flag;
+        if (!d_cc || !d_flag || !a.dist || !a.settled || !a.heap) {
+            gset_err("mn_graph_closeness: out of device memory (N = %d, %d sources at once)", N, chunk);
+            return -1;
+        }
+        GCHK(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+        GCHK(hipEventRecord(g->ev0, st));
+        for (int s0 = 0; s0 < N; s0 += chunk) {
+            a.s0 = s0;
+            a.n_src = std::min(chunk, N - s0);
+            // narrow workgroups until the launch has thousands of wavefronts, as the Brandes launch (one dependent chain per lane)
+            int lanes = 64;
+            if (const char *e = getenv("MN_CLOSENESS_LANES"))
+                lanes = std::max(1, std::min(64, atoi(e)));
+            else
+                while (lanes > 4 && (a.n_src + lanes - 1) / lanes < 4096)
+                    lanes >>= 1;
+            hipLaunchKernelGGL(k_clo_dijkstra, dim3((a.n_src + lanes - 1) / lanes), dim3(lanes), 0, st, a);
+        }
+        GCHK(hipMemcpyAsync(&ovf, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    GCHK(hipEventRecord(g->ev1, st));
+    GCHK(hipGetLastError());
+    GCHK(hipMemcpyAsync(out, d_cc, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    GCHK(hipStreamSynchronize(st));
+    if (ovf) {
+        gset_err("mn_graph_closeness: scratch overflow");
+        return -1;
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
+        g->last_ms = ms;
+    return 0;
+} MN_GUARD_END(gset_err, MN_NOTHING, -1)
+
+// deg_filter's loop (:667-680): one lane per node, the two lists summed in list order
+__global__ void __launch_bounds__(256) k_degree(DevGraph g, int normalized, double *in_deg, double *out_deg, double *degree,
+                                                double *centrality) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n)
+        return;
+    double in = 0, out = 0;
+    for (int e = g.off_out[i]; e < g.off_out[i + 1]; e++)
+        out += g.w_out ? g.w_out[e] : 1.0;
+    for (int e = g.off_in[i]; e < g.off_in[i + 1]; e++)
+        in += g.w_in ? g.w_in[e] : 1.0;
+    const double total = in + out;
+    double cent = total;
+    if (normalized && g.n > 1)
+        cent = total / (double)(g.n - 1);
+    in_deg[i] = in;
+    out_deg[i] = out;
+    degree[i] = total;
+    centrality[i] = cent;
+}
+
+extern "C" int mn_graph_degree(mn_graph *g, int normalized, double *in_deg, double *out_deg, double *degree, double *centrality) try {
+    GCHK(hipSetDevice(g->device));
+    const int N = g->n;
+    if (N == 0)
+        return 0;
+    hipStream_t st = g->stream;
+    double *d = nullptr;
+    GCHK(hipMalloc(&d, (size_t)4 * N * sizeof(double)));
+    hipLaunchKernelGGL(k_degree, dim3((N + 255) / 256), dim3(256), 0, st,
+                       DevGraph{N, g->off_out, g->tgt_out, g->w_out, g->off_in, g->tgt_in, g->w_in}, normalized ? 1 : 0, d, d + N,
+                       d + 2 * (size_t)N, d + 3 * (size_t)N);
+    hipError_t e = hipGetLastError();
+    double *dst[4] = {in_deg, out_deg, degree, centrality};
+    for (int k = 0; k < 4 && e == hipSuccess; k++)
+        if (dst[k])
+            e = hipMemcpyAsync(dst[k], d + (size_t)k * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    GCHK(e);
+    return 0;
+} MN_GUARD_END(gset_err, MN_NOTHING, -1)

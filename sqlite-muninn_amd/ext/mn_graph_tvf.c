@@ -580,3 +580,197 @@ int mn_register_betweenness_tvfs(sqlite3 *db) { /* two of centrality_register_tv
         rc = sqlite3_create_module(db, "graph_edge_betweenness", &edge_betweenness_module, 0);
     return rc;
 }
+
+/* ───────────────────────── graph_closeness / graph_degree (src/graph_centrality.c:1269-1504 and :544-750) ───────────────────────── */
+
+typedef struct {
+    sqlite3_vtab_cursor base;
+    char **ids; /* node ids, first-seen order (owned) */
+    int n_ids;
+    double *val[4]; /* closeness: centrality; degree: in_degree, out_degree, degree, centrality */
+    int n, pos, eof;
+} CenCursor;
+
+static void cen_clear(CenCursor *c) {
+    for (int i = 0; i < c->n_ids; i++)
+        free(c->ids[i]);
+    free(c->ids);
+    c->ids = 0;
+    for (int k = 0; k < 4; k++) {
+        free(c->val[k]);
+        c->val[k] = 0;
+    }
+    c->n_ids = c->n = 0;
+}
+
+static int cen_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
+    (void)v;
+    CenCursor *c = (CenCursor *)calloc(1, sizeof(CenCursor));
+    if (!c)
+        return SQLITE_NOMEM;
+    c->eof = 1;
+    *out = &c->base;
+    return SQLITE_OK;
+}
+static int cen_close(sqlite3_vtab_cursor *cur) {
+    cen_clear((CenCursor *)cur);
+    free(cur);
+    return SQLITE_OK;
+}
+static int cen_next(sqlite3_vtab_cursor *cur) {
+    CenCursor *c = (CenCursor *)cur;
+    c->pos++;
+    c->eof = c->pos >= c->n;
+    return SQLITE_OK;
+}
+static int cen_eof(sqlite3_vtab_cursor *cur) { return ((CenCursor *)cur)->eof; }
+static int cen_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
+    *out = ((CenCursor *)cur)->pos;
+    return SQLITE_OK;
+}
+
+/* hidden columns, in the order both TVFs declare them */
+enum { CH_EDGE_TABLE = 0, CH_SRC, CH_DST, CH_WEIGHT, CH_NORMALIZED, CH_DIRECTION, CH_TS, CH_T0, CH_T1, CH_COUNT };
+
+/* shared xFilter: degree = 0 → graph_closeness (normalized defaults to 1, direction to "forward", :1331 / :1370-1371),
+ * 1 → graph_degree (0 and "both", :607 / :646-647) */
+static int cen_filter_common(sqlite3_vtab_cursor *cur, int idxNum, int argc, sqlite3_value **argv, int degree) {
+    CenCursor *c = (CenCursor *)cur;
+    TvfVtab *vt = (TvfVtab *)cur->pVtab;
+    const char *who = degree ? "graph_degree" : "graph_closeness";
+    cen_clear(c);
+    c->pos = 0;
+    c->eof = 1;
+    if (argc < 3)
+        return SQLITE_OK;
+    const char *edge_table = 0, *src_col = 0, *dst_col = 0, *weight_col = 0, *direction = 0, *ts_col = 0;
+    sqlite3_value *t0 = 0, *t1 = 0;
+    int normalized = degree ? 0 : 1;
+    int pos = 0;
+    for (int bit = 0; bit < CH_COUNT && pos < argc; bit++) {
+        if (!(idxNum & (1 << bit)))
+            continue;
+        switch (bit) {
+        case CH_EDGE_TABLE: edge_table = val_text(argv[pos]); break;
+        case CH_SRC: src_col = val_text(argv[pos]); break;
+        case CH_DST: dst_col = val_text(argv[pos]); break;
+        case CH_WEIGHT: weight_col = val_text(argv[pos]); break;
+        case CH_NORMALIZED: normalized = sqlite3_value_int(argv[pos]); break;
+        case CH_DIRECTION: direction = val_text(argv[pos]); break;
+        case CH_TS: ts_col = val_text(argv[pos]); break;
+        case CH_T0: t0 = argv[pos]; break;
+        case CH_T1: t1 = argv[pos]; break;
+        }
+        pos++;
+    }
+    if (!direction)
+        direction = degree ? "both" : "forward";
+    mn_graph *g = 0;
+    char *err = 0;
+    int n = 0;
+    if (mn_sql_load_graph(vt->db, who, edge_table, src_col, dst_col, weight_col, direction, ts_col, t0, t1, &g, &c->ids, &n, &err) !=
+        SQLITE_OK) {
+        vt->base.zErrMsg = err ? err : sqlite3_mprintf("%s: failed to load graph", who);
+        return SQLITE_ERROR;
+    }
+    c->n_ids = n;
+    if (!g)
+        return SQLITE_OK; /* empty graph: no rows */
+    const int nval = degree ? 4 : 1;
+    int oom = 0;
+    for (int k = 0; k < nval; k++)
+        if (!(c->val[k] = (double *)calloc((size_t)n, sizeof(double))))
+            oom = 1;
+    if (oom) {
+        mn_graph_destroy(g);
+        return SQLITE_NOMEM;
+    }
+    int rc;
+    if (degree)
+        rc = mn_graph_degree(g, normalized, c->val[0], c->val[1], c->val[2], c->val[3]);
+    else
+        rc = mn_graph_closeness(g, !strcmp(direction, "both") ? 0 : !strcmp(direction, "reverse") ? 2 : 1, normalized, c->val[0]);
+    if (rc != 0) {
+        vt->base.zErrMsg = sqlite3_mprintf("%s: %s", who, mn_graph_last_error());
+        mn_graph_destroy(g);
+        return SQLITE_ERROR;
+    }
+    mn_graph_destroy(g);
+    c->n = n;
+    c->eof = n == 0;
+    return SQLITE_OK;
+}
+
+static int clos_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
+    (void)aux; (void)argc; (void)argv; (void)err;
+    return tvf_connect_with(db, "CREATE TABLE x("
+                                "  node TEXT, centrality REAL,"
+                                "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
+                                "  weight_col TEXT HIDDEN, normalized INTEGER HIDDEN,"
+                                "  direction TEXT HIDDEN, timestamp_col TEXT HIDDEN,"
+                                "  time_start HIDDEN, time_end HIDDEN"
+                                ")", out);
+}
+static int clos_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
+    (void)v;
+    return common_best_index(ii, 2, 10, 1000.0);
+}
+static int clos_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
+    (void)idxStr;
+    return cen_filter_common(cur, idxNum, argc, argv, 0);
+}
+static int clos_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
+    CenCursor *c = (CenCursor *)cur;
+    switch (col) {
+    case 0: sqlite3_result_text(ctx, c->ids[c->pos], -1, SQLITE_TRANSIENT); break;
+    case 1: sqlite3_result_double(ctx, c->val[0][c->pos]); break;
+    default: sqlite3_result_null(ctx); break;
+    }
+    return SQLITE_OK;
+}
+static sqlite3_module closeness_module = {
+    .iVersion = 0, .xCreate = 0, .xConnect = clos_connect, .xBestIndex = clos_best_index, .xDisconnect = tvf_disconnect,
+    .xDestroy = tvf_disconnect, .xOpen = cen_open, .xClose = cen_close, .xFilter = clos_filter, .xNext = cen_next,
+    .xEof = cen_eof, .xColumn = clos_column, .xRowid = cen_rowid,
+};
+
+static int degr_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
+    (void)aux; (void)argc; (void)argv; (void)err;
+    return tvf_connect_with(db, "CREATE TABLE x("
+                                "  node TEXT, in_degree REAL, out_degree REAL, degree REAL, centrality REAL,"
+                                "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
+                                "  weight_col TEXT HIDDEN, normalized INTEGER HIDDEN,"
+                                "  direction TEXT HIDDEN, timestamp_col TEXT HIDDEN,"
+                                "  time_start HIDDEN, time_end HIDDEN"
+                                ")", out);
+}
+static int degr_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
+    (void)v;
+    return common_best_index(ii, 5, 13, 1000.0);
+}
+static int degr_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
+    (void)idxStr;
+    return cen_filter_common(cur, idxNum, argc, argv, 1);
+}
+static int degr_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
+    CenCursor *c = (CenCursor *)cur;
+    if (col == 0)
+        sqlite3_result_text(ctx, c->ids[c->pos], -1, SQLITE_TRANSIENT);
+    else if (col >= 1 && col <= 4)
+        sqlite3_result_double(ctx, c->val[col - 1][c->pos]);
+    else
+        sqlite3_result_null(ctx);
+    return SQLITE_OK;
+}
+static sqlite3_module degree_module = {
+    .iVersion = 0, .xCreate = 0, .xConnect = degr_connect, .xBestIndex = degr_best_index, .xDisconnect = tvf_disconnect,
+    .xDestroy = tvf_disconnect, .xOpen = cen_open, .xClose = cen_close, .xFilter = degr_filter, .xNext = cen_next,
+    .xEof = cen_eof, .xColumn = degr_column, .xRowid = cen_rowid,
+};
+
+int mn_register_centrality_tvfs(sqlite3 *db) { /* the other two of centrality_register_tvfs (src/graph_centrality.c:1510-1530) */
+    int rc = sqlite3_create_module(db, "graph_degree", &degree_module, 0);
+    if (rc == SQLITE_OK)
+        rc = sqlite3_create_module(db, "graph_closeness", &closeness_module, 0);
+    return rc;
+}

@@ -67,6 +67,8 @@ GRAPH_SYMBOLS = [
     ("mn_graph_last_ms", C.c_double, [C.c_void_p]),
     ("mn_graph_out_edge_count", C.c_longlong, [C.c_void_p]),
     ("mn_graph_out_lists", C.c_int, [C.c_void_p, _i32p, _i32p]),
+    ("mn_graph_closeness", C.c_int, [C.c_void_p, C.c_int, C.c_int, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]),
+    ("mn_graph_degree", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mn_graph_pagerank", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_double, C.c_int, C.c_int,
                                     np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), C.POINTER(AlgoStats)]),
     ("mn_graph_components", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(AlgoStats)]),
@@ -155,6 +157,21 @@ class Graph:
         if self.L.mn_graph_betweenness(self.h, d, int(auto_approx), int(normalized), cb, eb.ctypes.data if edges else None) != 0:
             raise MuninnHipError(_gerr())
         return cb[:self.n], eb, self.L.mn_graph_last_ms(self.h)
+
+    def closeness(self, direction="forward", normalized=1):
+        """clo_filter's per-source loop (src/graph_centrality.c:1396-1434) → (cc[n], device ms)"""
+        cc = np.zeros(max(self.n, 1), np.float64)
+        d = {"both": 0, "forward": 1, "reverse": 2}[direction]
+        if self.L.mn_graph_closeness(self.h, d, int(normalized), cc) != 0:
+            raise MuninnHipError(_gerr())
+        return cc[:self.n], self.L.mn_graph_last_ms(self.h)
+
+    def degree(self, normalized=0):
+        """deg_filter's loop (src/graph_centrality.c:667-680) → (in_degree[n], out_degree[n], degree[n], centrality[n])"""
+        out = [np.zeros(max(self.n, 1), np.float64) for _ in range(4)]
+        if self.L.mn_graph_degree(self.h, int(normalized), *[a.ctypes.data for a in out]) != 0:
+            raise MuninnHipError(_gerr())
+        return tuple(a[:self.n] for a in out)
 
     def leiden(self, resolution=1.0, direction="both", mode=LEIDEN_SEQUENTIAL, batch=0):
         """run_leiden → (community[n] int32, Q, stats dict)"""
