@@ -26,11 +26,11 @@ tj = json.load(open(tj_path))
 for key, tag, name in (("leiden_lfr500k_unweighted_sync_default", tu, "unweighted"), ("leiden_lfr500k_weighted_sync_default", tw, "weighted")):
     ent = tj[key]
     (fk, nf), (wk, _) = total(tag, "f", "FETCH_SIZE"), total(tag, "w", "WRITE_SIZE")
-    ent["previous"] = {"traffic_bytes": ent["traffic_bytes"], "note": f"commit {ent['measured_at_commit']} (the Leiden kernels are the same; mn_graph.hip "
-                       "changed in its Brandes section, which made the file-level stamp stale, so the passes were run again)"}
+    ent["previous"] = {"traffic_bytes": ent["traffic_bytes"], "note": f"commit {ent['measured_at_commit']}"}
     ent["fetch_size_kb"], ent["write_size_kb"], ent["traffic_bytes"] = fk, wk, int((2 * fk + wk) * 1024)
     ent["source"] = (f"profiles/r04_leiden_500k_9M_{name}_pmc_summary.csv (round 4, last session: scripts/prof_leiden.sh, separate --pmc passes, "
                      f"{nf} launches of one run_leiden; FETCH_SIZE doubled)")
+    ent["kernel_sources"] = ["mn_leiden.hip", "mn_graph_int.hpp"]
     ent["kernel_sources_sha256"] = kernel_sources_sha(ent["kernel_sources"])
     ent["measured_in_round"], ent["measured_at_commit"] = 4, commit
     print(key, ent["traffic_bytes"], nf)

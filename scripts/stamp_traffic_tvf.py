@@ -62,7 +62,8 @@ def main():
     spec = {
         "tvf_pagerank_er_1000000_nodes_avg_degree_20": (["k_pr_pull_flat", "k_pr_pull_tile", "k_pr_pull", "k_pr_share"], 1, 100, ["mn_graph_algo.hip"]),
         "tvf_components_er_1000000_nodes_avg_degree_20": (["k_cc_hook", "k_cc_root", "k_cc_out", "k_uf_init"], 2, None, ["mn_graph_algo.hip"]),
-        "tvf_betweenness_er_20000_nodes_avg_degree_20": (["k_brandes_accumulate", "k_brandes_sources"], 2, None, ["mn_graph.hip"]),
+        "tvf_betweenness_er_20000_nodes_avg_degree_20": (["k_brandes_accumulate", "k_brandes_sources"], 2, None,
+                                                         ["mn_centrality.hip", "mn_graph_int.hpp", "mn_host.hpp"]),
     }
     for key, (names, runs, iters, srcs) in spec.items():
         if only and not any(o in key for o in only):

@@ -2,6 +2,7 @@
 // caller-supplied host all-gather for rehearsals.  See mn_comm.hpp.
 #include "mn_comm.hpp"
 #include "mn_guard.hpp"
+#include "mn_host.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -13,12 +14,10 @@
 
 static thread_local std::string g_cerr;
 static void cset_err(const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    mn_vformat(g_cerr, fmt, ap);
     va_end(ap);
-    g_cerr = buf;
 }
 const char *mn_comm_last_error_str() { return g_cerr.c_str(); }
 extern "C" const char *mn_comm_last_error(void) { return g_cerr.c_str(); }

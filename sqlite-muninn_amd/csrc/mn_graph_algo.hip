@@ -17,6 +17,7 @@
 // nothing changes and compresses: the same partition and sizes, component_id = smallest node index of the component.
 #include "../../include/muninn_hip.h"
 #include "mn_guard.hpp"
+#include "mn_host.hpp"
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -30,40 +31,14 @@
 
 static thread_local std::string g_aerr;
 static void aset_err(const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    mn_vformat(g_aerr, fmt, ap);
     va_end(ap);
-    g_aerr = buf;
 }
 extern "C" const char *mn_graph_algo_last_error(void) { return g_aerr.c_str(); }
 
-#define ACHK(expr)                                                                                 \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            aset_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return -1;                                                                             \
-        }                                                                                          \
-    } while (0)
-
-namespace {
-struct Bufs { // frees on scope exit
-    std::vector<void *> p;
-    template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess)
-            return nullptr;
-        p.push_back(q);
-        return static_cast<T *>(q);
-    }
-    ~Bufs() {
-        for (void *q : p)
-            (void)hipFree(q);
-    }
-};
-} // namespace
+#define ACHK(expr) MN_HIPCHK(aset_err, expr)
 
 // ───────────────────────── PageRank ─────────────────────────
 
@@ -319,7 +294,7 @@ extern "C" int mn_graph_pagerank(int n, int64_t n_edges, const int *src, const i
         toff.assign(1, 0);
     }
     const bool use_flat = tiles > 1 && flat;
-    Bufs b;
+    DevArena b;
     int *d_cut = tiles > 1 ? b.alloc<int>(cut.size()) : nullptr;
     if (tiles > 1 && !d_cut) {
         aset_err("mn_graph_pagerank: out of device memory");
@@ -596,7 +571,7 @@ extern "C" int mn_graph_components(int n, int64_t n_edges, const int *src, const
         return -1;
     }
     ACHK(hipSetDevice(device));
-    Bufs b;
+    DevArena b;
     int *d_src = b.alloc<int>((size_t)n_edges), *d_dst = b.alloc<int>((size_t)n_edges), *d_parent = b.alloc<int>(n), *d_rank = b.alloc<int>(n),
         *d_size = b.alloc<int>(n), *d_root = b.alloc<int>(n), *d_out = b.alloc<int>(n), *d_changed = b.alloc<int>(1);
     if (!d_src || !d_dst || !d_parent || !d_rank || !d_size || !d_root || !d_out || !d_changed) {
@@ -768,7 +743,7 @@ extern "C" int mn_csr_apply_delta(int old_node_count, const int *old_offsets, co
     }
     ACHK(hipSetDevice(device));
     const int E = n_old ? old_offsets[n_old] : 0;
-    Bufs b;
+    DevArena b;
     int *d_off = b.alloc<int>((size_t)n_old + 1), *d_tgt = b.alloc<int>(E), *d_vals = b.alloc<int>(nd), *d_vals_s = b.alloc<int>(nd),
         *d_dstart = b.alloc<int>(n_new), *d_cap = b.alloc<int>(n_new), *d_tmpoff = b.alloc<int>((size_t)n_new + 1), *d_cnt = b.alloc<int>(n_new),
         *d_newoff = b.alloc<int>((size_t)n_new + 1);

@@ -4,6 +4,7 @@
 // per-node metadata, the level RNG (src/hnsw_algo.c:19-30,240-248) and the cold delete path.
 #include "../../include/muninn_hip.h"
 #include "mn_guard.hpp"
+#include "mn_host.hpp"
 #include "mn_device.hpp"
 #include "mn_comm.hpp"
 
@@ -24,12 +25,10 @@
 static thread_local std::string g_err;
 
 static void set_err(const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    mn_vformat(g_err, fmt, ap);
     va_end(ap);
-    g_err = buf;
 }
 
 // ── host allocations of this library: countable, and the n-th one can be made to fail (test hook of the exception barrier,
@@ -58,14 +57,7 @@ extern "C" long long mn_debug_fault_alloc(long long nth) {
     return g_alloc_count.exchange(0, std::memory_order_relaxed);
 }
 
-#define HIPCHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e__ = (expr);                                                          \
-        if (e__ != hipSuccess) {                                                          \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return -1;                                                                    \
-        }                                                                                 \
-    } while (0)
+#define HIPCHK(expr) MN_HIPCHK(set_err, expr)
 
 template <typename T> struct DevBuf {
     T *p = nullptr;

@@ -16,6 +16,7 @@
 // LUT (:247-258, expf) — these are inputs of the hot loop, not part of it.
 #include "../../include/muninn_hip.h"
 #include "mn_guard.hpp"
+#include "mn_host.hpp"
 #include <hip/hip_runtime.h>
 #include <chrono>
 
@@ -285,23 +286,14 @@ __global__ void __launch_bounds__(64) k_n2v_normalize(float *syn0, int n, int di
 
 static thread_local std::string g_nerr;
 static void nset_err(const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    mn_vformat(g_nerr, fmt, ap);
     va_end(ap);
-    g_nerr = buf;
 }
 extern "C" const char *mn_node2vec_last_error(void) { return g_nerr.c_str(); }
 
-#define NCHK(expr)                                                                                 \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            nset_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return -1;                                                                             \
-        }                                                                                          \
-    } while (0)
+#define NCHK(expr) MN_HIPCHK(nset_err, expr)
 
 static unsigned h_xs32(unsigned *s) {
     unsigned x = *s;

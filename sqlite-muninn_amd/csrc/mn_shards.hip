@@ -8,6 +8,7 @@
 //   build : ids are split by shard and the shards are built side by side, one host thread per GPU.
 #include "../../include/muninn_hip.h"
 #include "mn_guard.hpp"
+#include "mn_host.hpp"
 #include "mn_device.hpp"
 
 #include <cstdarg>
@@ -19,21 +20,12 @@
 
 static thread_local std::string s_err;
 static void sset_err(const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    mn_vformat(s_err, fmt, ap);
     va_end(ap);
-    s_err = buf;
 }
-#define SCHK(expr)                                                                                   \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess) {                                                                     \
-            sset_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);    \
-            return -1;                                                                               \
-        }                                                                                            \
-    } while (0)
+#define SCHK(expr) MN_HIPCHK(sset_err, expr)
 
 struct ShardBuf { // per-shard device buffers, grown on demand (on that shard's GPU)
     float *q = nullptr;
