@@ -208,7 +208,7 @@ typedef struct {
     int64_t last_n_dist;     /* distance evaluations performed by that launch (device counter) */
     int64_t last_n_expanded; /* neighbour rows read by that launch */
     int64_t last_n_overflow; /* queries whose heaps exceeded workspace (must be 0) */
-    int64_t last_n_exact_rows; /* f32 rows read for those distances: last_n_dist minus the candidates the fp16 shadow's bound
+    int64_t last_n_exact_rows; /* f32 rows read for those distances: last_n_dist minus the candidates the coded shadow's bound
                                 * rejected (MN_LOWPREC_FILTER; equal to last_n_dist with the filter off) */
     int64_t last_n_rows_lanes4;  /* ... of which walked by 4 lanes per row, */
     int64_t last_n_rows_lanes8;  /* by 8 and */

@@ -174,7 +174,7 @@ struct WaveCtx {
     int rcap = 0, nr = 0;
     CoopCtx *coop = nullptr;
     int no_spec_rows = 0; // MN_SPEC_ROWS=0 (host): the helpers' rows are requested only once the visited probe has answered (A/B runs)
-    // beam_layer<LP>: the fp16 shadow's bound rejects candidates before their f32 rows are read (lp_on: this query may)
+    // beam_layer<LP>: the coded shadow's bound rejects candidates before their f32 rows are read (lp_on: this query may)
     int lp_on = 0;
     LoQuery lq = {0.0f, 0.0};
     unsigned long long n_skip = 0; // distances decided by the bound alone (counted in n_dist as well)
@@ -369,7 +369,7 @@ DEVI int greedy_layer(const MnDevIndex &ix, WaveCtx &w, int entry, int level, in
 
 // src/hnsw_algo.c:347-448.  Results are left in the result heap; the caller drains it.
 // LP (k_beam, search): once the results are full, a row's new candidates are first held against the worst result on a lower
-// bound from the fp16 shadow (lo_rows_bound); only those it cannot reject have their f32 rows read.  A rejected candidate has
+// bound from the coded shadow (lo_rows_bound); only those it cannot reject have their f32 rows read.  A rejected candidate has
 // d ≥ worst0 ≥ the worst at any later moment of the row, so the reference would not have pushed it either (see the pre-filter
 // below): same pushes in the same order, same counters.
 template <int ORDER, int NCH, bool COH = false, bool WIDE = false, bool LOG = false, bool LP = false>

@@ -11,7 +11,8 @@
 //   M_max — the reference grows lists without bound there — at which point the host re-strides the table.
 //   up_off   [cap]       int32 first pool row of the node, -1 when level == 0
 //   levels   [cap] int8, deleted [cap] u8, ids [cap] int64, dirty [cap] u8 (nodes to re-persist)
-//   vec_lo   [cap][ld]   fp16 shadow of vectors (row x = lo_meta.scale * vec_lo), only when mn_lo_enabled(ld)
+//   vec_lo   [cap][32 * mn_lo_lines(ld)] dwords: 10-bit coded shadow of vectors, three codes per dword, whole 128-byte lines
+//                        (x~_i = lo_meta.scale * code_i), only when mn_lo_enabled(ld)
 //   lo_meta  [cap]       MnLoMeta per row: scale, r_x = |x - x~|, bounds on |x|
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,19 +21,36 @@
 #define MN_WAVE 64
 
 // ───────── low-precision shadow of the vectors (the one definition of its format: DESIGN.md §2, §3.1) ─────────
-// Row x of the index has a 2-byte copy h (IEEE fp16) and a power-of-two scale s; the dequantised row is x~_i = fl32(f32(h_i) * s),
-// computed the same way where the shadow is written (k_prep_rows) and where it is read (lo_rows_bound).  The search uses it only
-// to REJECT candidates on a certified lower bound of the exact distance (mn_beam.hpp beam_layer<LP>): results are unchanged.
-typedef unsigned short mn_lo_t; // fp16 bits
+// Row x of the index has a copy in signed 10-bit codes c_i = clamp(rintf(x_i / s), -511, 511) under the row's own scale
+// s = fl32(max|x_i| / 511) (not a power of two: one would give away up to a bit).  Three codes share a dword, as signed fields at
+// bits 0, 10 and 20 (bits 30-31 zero): dword w of a row holds codes 3w, 3w+1, 3w+2.  A row is mn_lo_lines(ld) lines of 128 bytes =
+// 96 codes each; codes past ld are 0.  The dequantised row is x~_i = fl32(f32(c_i) * s) (mn_lo_deq), computed the same way where the
+// shadow is written (k_prep_rows) and where it is read (lo_rows_bound).  The search uses it only to REJECT candidates on a certified
+// lower bound of the exact distance (mn_beam.hpp beam_layer<LP>): results are unchanged.
+typedef unsigned mn_lo_t; // three codes
+#define MN_LO_BITS 10
+#define MN_LO_CMAX 511          // largest code magnitude
+#define MN_LO_LINE_CODES 96     // codes per 128-byte line
+#define MN_LO_LINE_WORDS 32
 struct __align__(16) MnLoMeta {
-    float scale; // s = 2^e
-    float resid; // r_x >= |x - x~| (rounded up); +inf: never filter this row (non-finite element, or |x| out of range)
+    float scale; // s
+    float resid; // r_x >= |x - x~| (rounded up); +inf: never filter this row (non-finite element, |x| out of range, or s zero / subnormal)
     float xn_lo; // cosine: sqrt(nb) rounded down, nb = the row's f32 norm (norms[]) the exact distance divides by; else |x| rounded down
     float xn_hi; // |x| rounded up
 };
-// rows shorter than this read faster in f32 than the extra pass costs; rows must be whole 128-byte lines of fp16
+// rows shorter than this read faster in f32 than the extra pass costs
 #define MN_LO_MIN_LD 192
 __host__ __device__ inline bool mn_lo_enabled(int ld) { return ld >= MN_LO_MIN_LD && (ld & 63) == 0; }
+__host__ __device__ inline int mn_lo_lines(int ld) { return (ld + MN_LO_LINE_CODES - 1) / MN_LO_LINE_CODES; }
+__host__ __device__ inline size_t mn_lo_row_words(int ld) { return (size_t)mn_lo_lines(ld) * MN_LO_LINE_WORDS; } // dwords per coded row
+// floats the query takes in the LDS of the search kernels: where the shadow exists, q is zero-padded to the coded row's length, so
+// that the padding codes of the last line meet zeros and nothing that lies behind q (ld = 768: nothing is added)
+__host__ __device__ inline int mn_lo_q_floats(int ld) { return mn_lo_enabled(ld) ? mn_lo_lines(ld) * MN_LO_LINE_CODES : ld; }
+// field f (0..2) of a coded dword, and the element it stands for
+__host__ __device__ inline int mn_lo_code(unsigned w, int f) { return (int)(w << (32 - MN_LO_BITS * (f + 1))) >> (32 - MN_LO_BITS); }
+__host__ __device__ inline unsigned mn_lo_pack(int c0, int c1, int c2) {
+    return ((unsigned)c0 & 0x3ffu) | (((unsigned)c1 & 0x3ffu) << 10) | (((unsigned)c2 & 0x3ffu) << 20);
+}
 constexpr int MN_ORDER_SSE_V = 0;  // muninn_hip.h mn_order
 constexpr int MN_ORDER_WAVE_V = 1;
 
@@ -53,7 +71,7 @@ struct MnDevIndex {
     int n_slots;
     int n_pool_rows;
     int has_deleted; // 0: no soft-deleted node exists — the per-candidate deleted[] gather of the searches is skipped
-    const mn_lo_t *vec_lo;   // [cap][ld] or null (see MnLoMeta)
+    const mn_lo_t *vec_lo;   // [cap][mn_lo_row_words(ld)] or null (see MnLoMeta)
     const MnLoMeta *lo_meta; // [cap] or null
 };
 
@@ -85,7 +103,7 @@ struct MnSearchArgs {
     int cand_gcap;
     uint2 *res_ovf;          // [nq][res_gcap]
     int res_gcap;
-    unsigned long long *counters; // [0] n_dist [1] n_expanded [2] overflowed queries [3] distances decided by the fp16 bound alone
+    unsigned long long *counters; // [0] n_dist [1] n_expanded [2] overflowed queries [3] distances decided by the shadow's bound alone
                                   // [4] [5] exact rows walked by 8 / by 16 lanes (k_beam<LP>, SSE order; [6] [7] spare)
     unsigned long long *q_counters; // or, when not null: [nq][MN_QC] [0..5] of the same per query, plain stores (a few queries answered into the
                                     // index's pinned host block: no counter memset before the launch, no copy after it)
@@ -121,7 +139,7 @@ void mn_module_touch_kernels();
 void mn_module_touch_seq();
 void mn_module_touch_spec();
 void mn_module_touch_build();
-// rows [first_slot, first_slot + n): |v|² (cosine, into norms_out) and, when ix.vec_lo is set, the fp16 shadow — one launch
+// rows [first_slot, first_slot + n): |v|² (cosine, into norms_out) and, when ix.vec_lo is set, the coded shadow — one launch
 void mn_launch_prep_rows(const MnDevIndex &ix, int first_slot, int n, float *norms_out, mn_lo_t *lo_out, MnLoMeta *meta_out,
                          hipStream_t st);
 int mn_launch_dist_batch(int metric, int order, const float *d_query, const float *d_rows, long long n, int dim, int ld,

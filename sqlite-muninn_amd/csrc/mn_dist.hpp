@@ -267,7 +267,7 @@ DEVI float sse_row(const float *__restrict__ row, const float *q_lds, int dim, i
     return sum;
 }
 
-// ───────────────────────── SSE order, a row spread over Q quads (the fp16 filter's survivors) ─────────────────────────
+// ───────────────────────── SSE order, a row spread over Q quads (the shadow filter's survivors) ─────────────────────────
 // beam_layer<LP> hands the exact walk a few rows per expansion (4.75 on average at 1M x 768, ef 128).  With 4 lanes per row and 12
 // float4 in flight per lane, a 768-float row is four DEPENDENT round trips to memory, each carrying a handful of rows.  Here a row
 // is given to Q = 2 or 4 quads (8 or 16 lanes): a stretch of Q·nb quad blocks is cut into Q contiguous pieces of nb ≤ 12 blocks,
@@ -730,18 +730,19 @@ DEVI float rows_distance_spread(const MnDevIndex &ix, const float *q_lds, float 
     return cosine_finish(dot, qnorm, nb);
 }
 
-// ───────────────────────── the fp16 shadow: a certified lower bound on the exact distance ─────────────────────────
+// ───────────────────────── the coded shadow: a certified lower bound on the exact distance ─────────────────────────
 // DESIGN.md §3.1 derives every factor below.  The approximate pass may sum in any order: the bound covers any order.
 
 // x~_i: the dequantised element, computed the same way by k_prep_rows (which derives r_x from it) and by the approximate pass
-DEVI float lo_deq(unsigned h, float s) { return __fmul_rn((float)__builtin_bit_cast(_Float16, (unsigned short)h), s); }
+DEVI float lo_deq(int c, float s) { return __fmul_rn((float)c, s); }
 DEVI double mn_gamma(int n) { // γ_n = n u / (1 - n u), u = 2^-24
     const double nu = (double)n * 0x1p-24;
     return nu / (1.0 - nu);
 }
 
 // UB lines of the row in flight per lane (8 lanes per row, 16 B each: one 128-byte line per row per load instruction), then the
-// sums: Σ q·x~ or Σ (q - x~)², f32, fused multiply-adds
+// sums: Σ q·x~ or Σ (q - x~)², f32, fused multiply-adds.  Lane c's uint4 of line k holds codes 96k + 12c .. 96k + 12c + 11 (dword j:
+// codes 3j .. 3j+2 of those, mn_device.hpp); `q` points at the lane's q[12c], read as three float4 per line.
 template <bool L2, int UB>
 DEVI void lo_lines(const uint4 *__restrict__ row, const float *q, float s, int lines, int &k, float &acc) {
     for (; k + UB <= lines; k += UB) {
@@ -752,13 +753,14 @@ DEVI void lo_lines(const uint4 *__restrict__ row, const float *q, float s, int l
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < UB; u++) {
-            const float4 qa = *reinterpret_cast<const float4 *>(q + 64 * (k + u));
-            const float4 qb = *reinterpret_cast<const float4 *>(q + 64 * (k + u) + 4);
-            const float qe[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+            const float4 qa = *reinterpret_cast<const float4 *>(q + MN_LO_LINE_CODES * (k + u));
+            const float4 qb = *reinterpret_cast<const float4 *>(q + MN_LO_LINE_CODES * (k + u) + 4);
+            const float4 qc = *reinterpret_cast<const float4 *>(q + MN_LO_LINE_CODES * (k + u) + 8);
+            const float qe[12] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w, qc.x, qc.y, qc.z, qc.w};
             const unsigned w4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const float x = lo_deq((e & 1) ? (w4[e >> 1] >> 16) : (w4[e >> 1] & 0xffffu), s);
+            for (int e = 0; e < 12; e++) {
+                const float x = lo_deq(mn_lo_code(w4[e / 3], e % 3), s); // v_bfe_i32, v_cvt_f32_i32, v_mul_f32
                 if (L2) {
                     const float d = __fsub_rn(qe[e], x);
                     acc = fmaf(d, d, acc);
@@ -766,13 +768,16 @@ DEVI void lo_lines(const uint4 *__restrict__ row, const float *q, float s, int l
                     acc = fmaf(qe[e], x, acc);
                 }
             }
-            __builtin_amdgcn_sched_barrier(0); // (q's LDS reads of the next line wait: 8 floats live, not 8 per line in flight)
+            __builtin_amdgcn_sched_barrier(0); // (q's LDS reads of the next line wait: 12 floats live, not 12 per line in flight)
         }
     }
 }
 
 // Approximate accumulations of n shadow rows (slot per lane, lanes < n valid) against q_lds; lane i < n gets row i's.  8 rows
 // per pass, lane (r, c) reads bytes 16c .. 16c+15 of every 128-byte line of row r.  `sc`: lane i < n holds row i's scale.
+// The last line of a row whose length is no multiple of 96 ends in zero codes; q_lds is zero-padded to the coded length
+// (mn_lo_q_floats: the search kernels' LDS carve) rather than the lanes past ld masked, so whatever lies behind q — a NaN bit
+// pattern times a zero code would be NaN — is never read and the loop carries no mask.
 template <bool L2>
 DEVI float lo_rows_accumulate(const MnDevIndex &ix, const float *q_lds, int myslot, float sc, int n, int lane) {
     float mine = 0.0f;
@@ -781,17 +786,18 @@ DEVI float lo_rows_accumulate(const MnDevIndex &ix, const float *q_lds, int mysl
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int c = ln & 7, r = ln >> 3;
-    const int lines = ix.ld >> 6;
+    const int lines = mn_lo_lines(ix.ld);
+    const size_t row_words = mn_lo_row_words(ix.ld);
     for (int t = 0; t < n; t += 8) {
         const int rr = t + r < n ? t + r : n - 1;
         const int sl = __shfl(myslot, rr);
         const float s = __shfl(sc, rr);
-        const uint4 *row = reinterpret_cast<const uint4 *>(ix.vec_lo + (size_t)sl * ix.ld) + c;
-        const float *q = q_lds + 8 * c;
+        const uint4 *row = reinterpret_cast<const uint4 *>(ix.vec_lo + (size_t)sl * row_words) + c;
+        const float *q = q_lds + 12 * c;
         float acc = 0.0f;
         int k = 0;
-        lo_lines<L2, 12>(row, q, s, lines, k, acc);
-        lo_lines<L2, 4>(row, q, s, lines, k, acc);
+        lo_lines<L2, 8>(row, q, s, lines, k, acc); // (768 codes: all 8 lines in flight before the first use)
+        lo_lines<L2, 2>(row, q, s, lines, k, acc);
         lo_lines<L2, 1>(row, q, s, lines, k, acc);
         acc += quad_xor1(acc);
         acc += quad_xor2(acc);

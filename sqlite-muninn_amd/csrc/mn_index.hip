@@ -121,7 +121,7 @@ struct mn_index {
     int ht_cap = 256;
     // device state
     DevBuf<float> d_vectors, d_norms;
-    DevBuf<mn_lo_t> d_vec_lo;    // fp16 shadow of d_vectors, grown with it (mn_lo_enabled(ld) only; mn_device.hpp MnLoMeta)
+    DevBuf<mn_lo_t> d_vec_lo;    // coded shadow of d_vectors (mn_lo_row_words(ld) dwords per row), grown with it (mn_lo_enabled(ld) only; mn_device.hpp MnLoMeta)
     DevBuf<MnLoMeta> d_lo_meta;
     DevBuf<int> d_links0, d_links_up, d_up_off;
     DevBuf<signed char> d_levels;
@@ -410,7 +410,7 @@ static int sync_meta(mn_index *x) {
     if (x->d_vectors.reserve(ns * x->ld, true, st, -1, hs * x->ld)) return -1;
     if (x->d_norms.reserve(ns, true, st, -1, hs)) return -1;
     if (mn_lo_enabled(x->ld)) {
-        if (x->d_vec_lo.reserve(ns * x->ld, true, st, -1, hs * x->ld)) return -1;
+        if (x->d_vec_lo.reserve(ns * mn_lo_row_words(x->ld), true, st, -1, hs * mn_lo_row_words(x->ld))) return -1;
         if (x->d_lo_meta.reserve(ns, true, st, -1, hs)) return -1;
     }
     if (x->d_links0.reserve(ns * x->W0, true, st, 0xFF, hs * x->W0)) return -1;
@@ -453,7 +453,7 @@ static int sync_meta(mn_index *x) {
     return 0;
 }
 
-// what is derived from rows [first, first + n) once they are in place: norms (cosine) and the fp16 shadow, one launch
+// what is derived from rows [first, first + n) once they are in place: norms (cosine) and the coded shadow, one launch
 static void prep_rows(mn_index *x, int first, int n) {
     mn_launch_prep_rows(dev_view(x), first, n, x->metric == MN_METRIC_COSINE ? x->d_norms.p : nullptr, x->d_vec_lo.p,
                         x->d_lo_meta.p, x->stream);
@@ -847,7 +847,7 @@ static int fetch_counters(mn_index *x) {
     x->last.last_n_dist = (int64_t)c[0];
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
-    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
+    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the shadow's bound decided alone)
     x->last.last_n_rows_lanes8 = (int64_t)c[4];
     x->last.last_n_rows_lanes16 = (int64_t)c[5];
     x->last.last_n_rows_lanes4 = x->last.last_n_exact_rows - (int64_t)(c[4] + c[5]);
@@ -966,7 +966,7 @@ static int counters_from(mn_index *x, const unsigned long long *c) {
     x->last.last_n_dist = (int64_t)c[0];
     x->last.last_n_expanded = (int64_t)c[1];
     x->last.last_n_overflow = (int64_t)c[2];
-    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the fp16 bound decided alone)
+    x->last.last_n_exact_rows = (int64_t)(c[0] - c[3]); // ([3]: distances the shadow's bound decided alone)
     x->last.last_n_rows_lanes4 = x->last.last_n_exact_rows; // (the few-queries kernels walk every row with 4 lanes)
     x->last.last_n_rows_lanes8 = x->last.last_n_rows_lanes16 = 0;
     return 0;

@@ -1,6 +1,6 @@
 // mn_kernels.hip — hand-written gfx950 kernels for sqlite-muninn's HNSW hot path.
 //
-//   k_prep_rows    |v|² per row in the index's summation order (cosine) and the fp16 shadow of the row
+//   k_prep_rows    |v|² per row in the index's summation order (cosine) and the 10-bit coded shadow of the row
 //   k_dist_batch   vec_*_distance(query, rows[i])                       src/vec_math.c:78-143
 //   k_beam         greedy descent + ef-bounded beam search, one 64-lane wavefront per query
 //                  (search flavour: hnsw_search src/hnsw_algo.c:670-704; build flavour: the search
@@ -26,7 +26,7 @@
 #include "mn_dist.hpp"
 
 // ───────────────────────── k_prep_rows ─────────────────────────
-// Everything derived from a row when it is written (upload_vectors): |v|² in the index's order (cosine) and the fp16 shadow
+// Everything derived from a row when it is written (upload_vectors): |v|² in the index's order (cosine) and the coded shadow
 // (MnLoMeta, mn_device.hpp).  One wavefront per row, one launch per upload — a one-row INSERT gets no extra launch.
 
 DEVI double wave_sum_f64(double v) {
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(64)
     }
     if (!lo_out)
         return;
-    // scale 2^e: the largest element lands in [2^14, 2^15) of fp16 (max 65504)
+    // the row's own scale: the largest element gets code ±511
     float mx = 0.0f;
     bool bad = false;
     for (int i = lane; i < ix.ld; i += 64) {
@@ -68,22 +68,32 @@ __global__ void __launch_bounds__(64)
     for (int m = 32; m >= 1; m >>= 1)
         mx = fmaxf(mx, __shfl_xor(mx, m));
     bad = __ballot(bad) != 0;
-    int e = 0;
-    if (!bad && mx > 0.0f) {
-        e = ilogbf(mx) - 14;
-        e = e < -140 ? -140 : (e > 127 ? 127 : e);
-    }
-    const float s = ldexpf(1.0f, e);
+    float s = __fdiv_rn(mx, (float)MN_LO_CMAX);
+    // zero, subnormal (x~ = c s would depend on the flush mode) or not finite: the row is coded as zeros and never filtered
+    bad |= !(s >= 1.17549435e-38f && s <= 3.4028235e38f);
+    if (bad)
+        s = 0.0f;
     double r2 = 0.0, x2 = 0.0;
-    mn_lo_t *lo = lo_out + (size_t)slot * ix.ld;
-    for (int i = lane; i < ix.ld; i += 64) {
-        const float v = lds[i];
-        const _Float16 h = bad ? (_Float16)0.0f : (_Float16)ldexpf(v, -e);
-        const unsigned short hb = __builtin_bit_cast(unsigned short, h);
-        lo[i] = hb;
-        const double dv = (double)v - (double)lo_deq(hb, s); // exact: both are f32 values, and x~ ≈ x
-        r2 += dv * dv;
-        x2 += (double)v * (double)v;
+    mn_lo_t *lo = lo_out + (size_t)slot * mn_lo_row_words(ix.ld);
+    const int words = (int)mn_lo_row_words(ix.ld);
+    for (int w = lane; w < words; w += 64) { // dword w: codes 3w, 3w+1, 3w+2; past ld: 0
+        int c[3];
+#pragma unroll
+        for (int f = 0; f < 3; f++) {
+            const int i = 3 * w + f;
+            c[f] = 0;
+            if (i < ix.ld) {
+                const float v = lds[i];
+                if (!bad) {
+                    const float t = rintf(__fdiv_rn(v, s));
+                    c[f] = (int)fminf(fmaxf(t, -(float)MN_LO_CMAX), (float)MN_LO_CMAX);
+                }
+                const double dv = (double)v - (double)lo_deq(c[f], s); // exact: both are f32 values, and x~ ≈ x
+                r2 += dv * dv;
+                x2 += (double)v * (double)v;
+            }
+        }
+        lo[w] = mn_lo_pack(c[0], c[1], c[2]);
     }
     r2 = wave_sum_f64(r2);
     x2 = wave_sum_f64(x2);
@@ -216,7 +226,7 @@ int mn_launch_dist_batch(int metric, int order, const float *d_query, const floa
 
 // one query, one (leading) wavefront; `coop` = the group's shared area when helpers stand by (k_beam_coop)
 // LAT: a latency-bound launch (few queries, one workgroup each): the layer searches keep their queues in registers (beam_layer_auto)
-// LP: the layer-0 search of a batch filters on the fp16 shadow first (beam_layer<LP>)
+// LP: the layer-0 search of a batch filters on the coded shadow first (beam_layer<LP>)
 template <int ORDER, int NCH, bool BUILD, bool WIDE, bool LAT = false, bool LP = false>
 DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long long qi, const int lane, unsigned char *smem,
                      CoopCtx *coop, unsigned *lds_bitmap = nullptr) {
@@ -225,7 +235,8 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
     uint2 *res_l = cand_l + MN_CAND_LDS;
     int *scratch = reinterpret_cast<int *>(res_l + MN_RES_LDS);
     float *q = reinterpret_cast<float *>(scratch + 64);
-    float *tile = q + ix.ld; // SSE order only (mn_search_lds_bytes)
+    const int qf = mn_lo_q_floats(ix.ld); // ld, or the coded row's length: zeros behind ld for lo_rows_accumulate
+    float *tile = q + qf; // SSE order only (mn_search_lds_bytes)
 
     int qslot = -1;
     const float *qsrc;
@@ -235,7 +246,7 @@ DEVI void beam_query(const MnDevIndex &ix, const MnSearchArgs &a, const long lon
     } else {
         qsrc = a.queries + (size_t)qi * ix.dim;
     }
-    for (int i = lane; i < ix.ld; i += 64)
+    for (int i = lane; i < qf; i += 64)
         q[i] = i < ix.dim ? qsrc[i] : 0.0f;
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
@@ -414,7 +425,7 @@ __global__ void __launch_bounds__(MN_COOP_WAVES * 64) k_beam_coop(MnDevIndex ix,
 }
 
 size_t mn_search_lds_bytes(int ld, bool tile) {
-    size_t b = (size_t)(MN_CAND_LDS + MN_RES_LDS) * sizeof(uint2) + 64 * sizeof(int) + (size_t)ld * sizeof(float);
+    size_t b = (size_t)(MN_CAND_LDS + MN_RES_LDS) * sizeof(uint2) + 64 * sizeof(int) + (size_t)mn_lo_q_floats(ld) * sizeof(float);
     if (tile)
         b += MN_TILE_FLOATS * sizeof(float);
     // tuning knob: extra (unused) LDS per wavefront lowers the waves resident per CU
@@ -518,7 +529,7 @@ static void launch_beam(const MnDevIndex &ix, const MnSearchArgs &a, bool build,
             launch_coop<ORDER, NCH, false, false>(ix, a, base, tot, st);
         return;
     }
-    // a search over an index with the fp16 shadow: reject on its bound first (MN_LOWPREC_FILTER=0: never; read per launch, so
+    // a search over an index with the coded shadow: reject on its bound first (MN_LOWPREC_FILTER=0: never; read per launch, so
     // that one process can A/B the two)
     const char *lp = getenv("MN_LOWPREC_FILTER");
     if (!build && ix.vec_lo && ix.lo_meta && !(lp && atoi(lp) == 0)) {
