@@ -233,6 +233,37 @@ int mn_dev_download(mn_index *idx, void *dst_host, const void *src_dev, size_t b
  * d_queries device [nq][dim]; out host [nq][k] ids. */
 int mn_hnsw_bruteforce_topk(mn_index *idx, const float *d_queries, int64_t nq, int k, int64_t *out_ids);
 
+/* ---- exact (flat) search ----
+ * No reference function stands behind these entry points: the reference answers a query only through its graph
+ * (hnsw_search, src/hnsw_algo.c:670-704) and computes exact neighbours nowhere but in its benchmark harness, on the CPU.  What
+ * they are held to instead is the index's own distance: for every query, d(x) = the value mn_vec_dist_batch returns for the
+ * index's metric and order, bit for bit, over all live (non-deleted) slots; the answer is the k smallest under (d ascending as
+ * floats, then slot = insertion order ascending), ids and those f32 distances.  1 <= k <= 128.  Output layout of
+ * mn_hnsw_search_batch, except that the unused tail of a query with fewer than k live rows is id -1, distance +inf.
+ * allow_ids (NULL: no filter): only rows whose id is listed can be returned; unknown and deleted ids are ignored, n_allow = 0
+ * with a non-NULL pointer answers nothing.  allow_ids is a HOST array in both calls.
+ * The graph and every other piece of index state are left as they were.  DESIGN.md §3.6: a pass on the f32 matrix cores ranks
+ * every row by a certified lower bound of d, a short list is re-scored in the index's order, and a per-query certificate
+ * proves that no row outside the list could enter the answer; queries it fails for — exact ties at the k-th place among
+ * them — and k > 32 run the index's inner loop over every row.  MN_EXACT=valu forces that loop for every query,
+ * MN_EXACT_SLACK=<n> sets the list's surplus over k (default 16); both are read per call. */
+typedef struct {
+    int64_t n_queries, n_mfma_queries, n_fallback_queries, n_rescored_rows, n_bound_violations;
+    float kernel_ms;
+} mn_exact_stats;
+int mn_hnsw_search_exact_batch(mn_index *idx, const float *queries, int64_t nq, int k,
+                               const int64_t *allow_ids, int64_t n_allow,   /* allow_ids NULL: no filter */
+                               int64_t *out_ids, float *out_dists, int *out_counts);
+/* queries and outputs in device memory on idx's device.  Queued on the index's stream, but the call returns only once its
+ * kernels have finished: the host reads how many queries failed their certificate before it launches their pass. */
+int mn_hnsw_search_exact_batch_dev(mn_index *idx, const float *d_queries, int64_t nq, int k,
+                                   const int64_t *allow_ids, int64_t n_allow,
+                                   int64_t *d_out_ids, float *d_out_dists, int *d_out_counts);
+/* counters of the last exact search on this index: queries asked, queries that took the matrix-core pass, queries whose
+ * certificate failed, rows re-scored, and rows whose exact distance lay below their bound (a check of the derivation on every
+ * row touched: always 0); kernel_ms = HIP-event time of the call's kernels. */
+int mn_hnsw_last_exact(mn_index *idx, mn_exact_stats *out);
+
 /* ---- graph_csr.h / graph_community.c replacements (a18-a22) ---- */
 typedef struct mn_graph mn_graph; /* device-resident adjacency: GraphData.out / .in (src/graph_load.h:27-37) as two
                                      CsrArray (src/graph_csr.h:27-34: int32 offsets[V+1], int32 targets[E], f64 weights[E]|NULL) */

@@ -160,6 +160,19 @@ size_t mn_brute_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int k, in
 int mn_launch_bruteforce_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, long long *d_out_ids,
                               void *scratch, hipStream_t st);
 
+// exact search (mn_exact.hip).  Candidate pass on the matrix cores + re-score + certificate: kp = k + slack <= 64 list entries per
+// query, scratch = one allocation of mn_exact_mfma_scratch_bytes(), d_ctr [3] zeroed ([0] marked queries [1] rows re-scored [2] bound
+// violations), d_marked [nq].  Returns 1 when the device does not grant the LDS the lists need (nothing launched), else 0 / -1.
+size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp);
+int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, int kp, const unsigned *d_allow,
+                         void *scratch, long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr,
+                         int *d_marked, hipStream_t st);
+// the index's inner loop over every row for queries d_qsel[0..n) (null: 0..n-1), k <= 128; same LDS as k_bruteforce
+size_t mn_exact_valu_lds_bytes(int ld);
+int mn_launch_exact_valu(const MnDevIndex &ix, const float *d_queries, const int *d_qsel, long long n, int k, const unsigned *d_allow,
+                         long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
+void mn_launch_exact_fill(long long nq, int k, long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
+
 // sharded index (config 3): per-shard top-k lists gathered as [world][nq][k] → global top-k per query in the total order
 // (distance, shard rank, position)  (mn_kernels.hip)
 // synchronises the index's stream; *n_overflow = queries of its last search that exceeded their heap workspace.  0 / -1

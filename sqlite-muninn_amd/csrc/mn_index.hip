@@ -173,6 +173,7 @@ struct mn_index {
     long long last_spec_searched = 0; // searches the last speculative build ran (≥ nodes inserted)
     bool broken = false; // an insert failed after its kernels had begun to rewrite link rows: nothing can be trusted
     mn_launch_stats last = {0, 0, 0, 0, 0, 0, 0, 0};
+    mn_exact_stats last_exact = {0, 0, 0, 0, 0, 0.0f}; // counters of the last mn_hnsw_search_exact_batch[_dev]
 };
 
 // ───────────────────────── small host helpers ─────────────────────────
@@ -2409,5 +2410,129 @@ extern "C" int mn_hnsw_bruteforce_topk(mn_index *x, const float *d_queries, int6
     }
     HIPCHK(hipMemcpyAsync(out_ids, x->ws_outi.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return 0;
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
+
+// ───────────────────────── exact search (mn_exact.hip) ─────────────────────────
+
+namespace {
+struct ExactScratch { // one device allocation per call, released on every way out
+    DevBuf<unsigned char> b;
+    ~ExactScratch() { b.release(); }
+};
+} // namespace
+
+static int exact_search_dev(mn_index *x, const float *d_queries, int64_t nq, int k, const int64_t *allow_ids, int64_t n_allow,
+                            int64_t *d_ids, float *d_dists, int *d_counts) {
+    if (k < 1 || k > 128 || nq < 0 || n_allow < 0) {
+        set_err("mn_hnsw_search_exact: k must be 1..128 (got %d), nq and n_allow >= 0", k);
+        return -1;
+    }
+    if (push_links(x) || sync_meta(x))
+        return -1;
+    x->last_exact = {nq, 0, 0, 0, 0, 0.0f};
+    if (nq == 0)
+        return 0;
+    hipStream_t st = x->stream;
+    if (x->n_slots == 0) {
+        mn_launch_exact_fill(nq, k, (long long *)d_ids, d_dists, d_counts, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    const char *force = getenv("MN_EXACT");       // "valu": the index's inner loop over every row for every query
+    const char *slack_e = getenv("MN_EXACT_SLACK"); // list entries beyond k (0: most certificates fail)
+    int slack = slack_e ? atoi(slack_e) : 16;
+    if (slack < 0)
+        slack = 0;
+    const int kp = std::min(k + slack, 64);
+    bool mfma = k <= 32 && !(force && !strcmp(force, "valu"));
+    MnDevIndex v = dev_view(x);
+    // the allow-list as one bit per slot
+    const size_t words = allow_ids ? ((size_t)x->n_slots + 31) / 32 : 0;
+    std::vector<unsigned> bits(words, 0u);
+    for (int64_t i = 0; allow_ids && i < n_allow; i++) {
+        const int s = ht_find(x, allow_ids[i]);
+        if (s >= 0 && !x->deleted[s])
+            bits[(size_t)s >> 5] |= 1u << (s & 31);
+    }
+    const size_t b_mfma = mfma ? mn_exact_mfma_scratch_bytes(v, nq, kp) : 0;
+    const size_t b_bits = (words * 4 + 255) & ~(size_t)255, b_marked = ((size_t)nq * 4 + 255) & ~(size_t)255;
+    ExactScratch sc;
+    if (sc.b.reserve(b_mfma + b_bits + b_marked + 256, false, st))
+        return -1;
+    unsigned char *p = sc.b.p + b_mfma;
+    unsigned *d_allow = allow_ids ? reinterpret_cast<unsigned *>(p) : nullptr;
+    p += b_bits;
+    int *d_marked = reinterpret_cast<int *>(p);
+    p += b_marked;
+    unsigned long long *d_ctr = reinterpret_cast<unsigned long long *>(p);
+    if (words)
+        HIPCHK(hipMemcpyAsync(d_allow, bits.data(), words * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_ctr, 0, 4 * sizeof(unsigned long long), st));
+    HIPCHK(hipEventRecord(x->ev0, st));
+    if (mfma) {
+        const int rc = mn_launch_exact_mfma(v, d_queries, nq, k, kp, d_allow, sc.b.p, (long long *)d_ids, d_dists, d_counts, d_ctr,
+                                            d_marked, st);
+        if (rc < 0) {
+            set_err("mn_hnsw_search_exact: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+            (void)hipStreamSynchronize(st);
+            return -1;
+        }
+        mfma = rc == 0;
+    }
+    unsigned long long ctr[3] = {0, 0, 0};
+    if (mfma) {
+        HIPCHK(hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // the marked queries alone, in one launch
+        if (mn_launch_exact_valu(v, d_queries, d_marked, (long long)ctr[0], k, d_allow, (long long *)d_ids, d_dists, d_counts, st)) {
+            set_err("mn_hnsw_search_exact: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+            (void)hipStreamSynchronize(st);
+            return -1;
+        }
+    } else if (mn_launch_exact_valu(v, d_queries, nullptr, nq, k, d_allow, (long long *)d_ids, d_dists, d_counts, st)) {
+        set_err("mn_hnsw_search_exact: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(st);
+        return -1;
+    }
+    HIPCHK(hipEventRecord(x->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, x->ev0, x->ev1) != hipSuccess)
+        ms = 0;
+    x->last_exact = {nq, mfma ? nq : 0, (int64_t)ctr[0], (int64_t)ctr[1], (int64_t)ctr[2], ms};
+    return 0;
+}
+
+extern "C" int mn_hnsw_search_exact_batch_dev(mn_index *x, const float *d_queries, int64_t nq, int k, const int64_t *allow_ids,
+                                              int64_t n_allow, int64_t *d_ids, float *d_dists, int *d_counts) try {
+    if (use_device(x))
+        return -1;
+    return exact_search_dev(x, d_queries, nq, k, allow_ids, n_allow, d_ids, d_dists, d_counts);
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
+
+extern "C" int mn_hnsw_search_exact_batch(mn_index *x, const float *queries, int64_t nq, int k, const int64_t *allow_ids,
+                                          int64_t n_allow, int64_t *out_ids, float *out_dists, int *out_counts) try {
+    if (use_device(x))
+        return -1;
+    if (nq <= 0 || k < 1 || k > 128)
+        return exact_search_dev(x, nullptr, nq, k, allow_ids, n_allow, nullptr, nullptr, nullptr);
+    hipStream_t st = x->stream;
+    if (x->ws_q.reserve((size_t)nq * x->dim, false, st) || x->ws_outi.reserve((size_t)nq * k, false, st) ||
+        x->ws_outd.reserve((size_t)nq * k, false, st) || x->ws_outc.reserve((size_t)nq, false, st))
+        return -1;
+    HIPCHK(hipMemcpyAsync(x->ws_q.p, queries, (size_t)nq * x->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    if (exact_search_dev(x, x->ws_q.p, nq, k, allow_ids, n_allow, (int64_t *)x->ws_outi.p, x->ws_outd.p, x->ws_outc.p))
+        return -1;
+    HIPCHK(hipMemcpyAsync(out_ids, x->ws_outi.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_dists, x->ws_outd.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_counts, x->ws_outc.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
+
+extern "C" int mn_hnsw_last_exact(mn_index *x, mn_exact_stats *out) try {
+    *out = x->last_exact;
     return 0;
 } MN_GUARD_END(set_err, MN_NOTHING, -1)

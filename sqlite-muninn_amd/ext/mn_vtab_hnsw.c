@@ -1079,10 +1079,18 @@ static sqlite3_module hnsw_module = {
  * eponymous table-valued function exposes the batched device search without touching hnsw_index:
  *   SELECT query_idx, id, distance FROM hnsw_search_batch
  *    WHERE tbl = 'vec' AND queries = :blob AND k = 10 [AND ef_search = 128];
- * `queries` is nq * dimensions little-endian f32; rows come out grouped by query_idx, ascending distance. */
+ * `queries` is nq * dimensions little-endian f32; rows come out grouped by query_idx, ascending distance.
+ *
+ * hnsw_search_exact is the same function over the exact search (mn_hnsw_search_exact_batch: the true k nearest live rows, ties
+ * by insertion order, distances with the bits of the table's own metric), with an optional list of rowids to search among in
+ * place of ef_search:
+ *   SELECT query_idx, id, distance FROM hnsw_search_exact
+ *    WHERE tbl = 'vec' AND queries = :blob AND k = 10 [AND allow = :int64_blob];
+ * `allow` is n little-endian int64 rowids; rowids the table does not hold are ignored, an empty blob answers nothing. */
 typedef struct {
     sqlite3_vtab base;
     sqlite3 *db;
+    int exact; /* hnsw_search_exact: the fourth hidden column is `allow` */
 } BatchVtab;
 typedef struct {
     sqlite3_vtab_cursor base;
@@ -1094,9 +1102,11 @@ typedef struct {
 enum { BC_QIDX = 0, BC_ID, BC_DIST, BC_TBL, BC_QUERIES, BC_K, BC_EF };
 
 static int b_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    (void)aux; (void)argc; (void)argv; (void)err;
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(query_idx INTEGER, id INTEGER, distance REAL, tbl TEXT HIDDEN,"
-                                      " queries BLOB HIDDEN, k INTEGER HIDDEN, ef_search INTEGER HIDDEN)");
+    (void)argc; (void)argv; (void)err;
+    int rc = sqlite3_declare_vtab(db, aux ? "CREATE TABLE x(query_idx INTEGER, id INTEGER, distance REAL, tbl TEXT HIDDEN,"
+                                            " queries BLOB HIDDEN, k INTEGER HIDDEN, allow BLOB HIDDEN)"
+                                          : "CREATE TABLE x(query_idx INTEGER, id INTEGER, distance REAL, tbl TEXT HIDDEN,"
+                                            " queries BLOB HIDDEN, k INTEGER HIDDEN, ef_search INTEGER HIDDEN)");
     if (rc != SQLITE_OK)
         return rc;
     BatchVtab *v = (BatchVtab *)sqlite3_malloc((int)sizeof(BatchVtab));
@@ -1104,6 +1114,7 @@ static int b_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, 
         return SQLITE_NOMEM;
     memset(v, 0, sizeof(*v));
     v->db = db;
+    v->exact = aux != 0;
     *out = &v->base;
     return SQLITE_OK;
 }
@@ -1173,6 +1184,7 @@ static int b_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, in
     int qbytes = sqlite3_value_bytes(argv[1]);
     int k = sqlite3_value_int(argv[2]);
     int ef = (idxNum & 0x8) && argc >= 4 ? sqlite3_value_int(argv[3]) : 2 * k;
+    const char *fn = bv->exact ? "hnsw_search_exact" : "hnsw_search_batch";
     VtabHnsw *v = tbl ? live_find(bv->db, tbl) : 0;
     if (!v && tbl) { /* not connected yet on this connection: touching the table connects it */
         char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", tbl);
@@ -1181,16 +1193,23 @@ static int b_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, in
         v = live_find(bv->db, tbl);
     }
     if (!v) {
-        bv->base.zErrMsg = sqlite3_mprintf("hnsw_search_batch: no hnsw_index table named '%s'", tbl ? tbl : "");
+        bv->base.zErrMsg = sqlite3_mprintf("%s: no hnsw_index table named '%s'", fn, tbl ? tbl : "");
         return SQLITE_ERROR;
     }
     if (flush_pending(v) != SQLITE_OK) {
-        bv->base.zErrMsg = sqlite3_mprintf("hnsw_search_batch: %s", v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
+        bv->base.zErrMsg = sqlite3_mprintf("%s: %s", fn, v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
         return SQLITE_ERROR;
     }
     int row = v->dim * (int)sizeof(float);
     if (k <= 0 || qbytes <= 0 || qbytes % row != 0) {
-        bv->base.zErrMsg = sqlite3_mprintf("hnsw_search_batch: queries must be a multiple of %d bytes (%d-dim f32), got %d", row, v->dim, qbytes);
+        bv->base.zErrMsg = sqlite3_mprintf("%s: queries must be a multiple of %d bytes (%d-dim f32), got %d", fn, row, v->dim, qbytes);
+        return SQLITE_ERROR;
+    }
+    const int has_allow = bv->exact && (idxNum & 0x8) && argc >= 4 && sqlite3_value_type(argv[3]) != SQLITE_NULL;
+    const int64_t *allow = has_allow ? (const int64_t *)sqlite3_value_blob(argv[3]) : 0;
+    const int abytes = has_allow ? sqlite3_value_bytes(argv[3]) : 0;
+    if (abytes % 8 != 0) {
+        bv->base.zErrMsg = sqlite3_mprintf("%s: allow must be a multiple of 8 bytes (int64 rowids), got %d", fn, abytes);
         return SQLITE_ERROR;
     }
     c->nq = qbytes / row;
@@ -1200,8 +1219,11 @@ static int b_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, in
     c->counts = (int *)malloc((size_t)c->nq * sizeof(int));
     if (!c->ids || !c->dists || !c->counts)
         return SQLITE_NOMEM;
-    if (mn_hnsw_search_batch(v->index, q, c->nq, k, ef, c->ids, c->dists, c->counts) != 0) {
-        bv->base.zErrMsg = sqlite3_mprintf("hnsw_search_batch: %s", mn_last_error());
+    static const int64_t none = 0; /* an empty blob has no address: any non-NULL pointer says "filter, nothing allowed" */
+    if ((bv->exact ? mn_hnsw_search_exact_batch(v->index, q, c->nq, k, has_allow ? (abytes ? allow : &none) : 0, abytes / 8,
+                                                c->ids, c->dists, c->counts)
+                   : mn_hnsw_search_batch(v->index, q, c->nq, k, ef, c->ids, c->dists, c->counts)) != 0) {
+        bv->base.zErrMsg = sqlite3_mprintf("%s: %s", fn, mn_last_error());
         return SQLITE_ERROR;
     }
     b_skip_empty(c);
@@ -1317,5 +1339,7 @@ int mn_register_hnsw_module(sqlite3 *db) {
         rc = sqlite3_create_module(db, "hnsw0", &hnsw_module, 0); /* alias named by BASELINE.json */
     if (rc == SQLITE_OK)
         rc = sqlite3_create_module(db, "hnsw_search_batch", &batch_module, 0); /* additive batch surface */
+    if (rc == SQLITE_OK)
+        rc = sqlite3_create_module(db, "hnsw_search_exact", &batch_module, (void *)&batch_module); /* non-NULL aux: the exact flavour */
     return rc;
 }

@@ -37,6 +37,11 @@ class LaunchStats(C.Structure):
                 ("last_n_rows_lanes4", C.c_int64), ("last_n_rows_lanes8", C.c_int64), ("last_n_rows_lanes16", C.c_int64)]
 
 
+class ExactStats(C.Structure):  # mn_exact_stats
+    _fields_ = [("n_queries", C.c_int64), ("n_mfma_queries", C.c_int64), ("n_fallback_queries", C.c_int64),
+                ("n_rescored_rows", C.c_int64), ("n_bound_violations", C.c_int64), ("kernel_ms", C.c_float)]
+
+
 class BuildStats(C.Structure):
     _fields_ = [("search_ms", C.c_double), ("link_ms", C.c_double), ("n_dist", C.c_int64), ("n_expanded", C.c_int64),
                 ("batches", C.c_int64), ("nodes", C.c_int64)]
@@ -97,6 +102,11 @@ SYMBOLS = [
     ("mn_dev_upload", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("mn_dev_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("mn_hnsw_bruteforce_topk", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _i64p]),
+    ("mn_hnsw_search_exact_batch", C.c_int,
+     [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, _i64p, _f32p, _i32p]),
+    ("mn_hnsw_search_exact_batch_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mn_hnsw_last_exact", C.c_int, [C.c_void_p, C.POINTER(ExactStats)]),
     # multi-GPU
     ("mn_comm_unique_id", C.c_int, [C.c_void_p]),
     ("mn_comm_init_rccl", C.c_void_p, [C.c_int, C.c_int, C.c_void_p, C.c_int]),
@@ -305,6 +315,45 @@ class HnswIndex:
         return ids, ds, cnt
 
     search_many = search_batch
+
+    # ---- exact (flat) search: the k nearest live rows under (distance, insertion order), bits of the index's own distance ----
+    @staticmethod
+    def _allow(allow):
+        """(pointer or None, count, keep-alive): allow=None means no filter, an empty list answers nothing."""
+        if allow is None:
+            return None, 0, None
+        a = np.ascontiguousarray(allow, np.int64).reshape(-1)
+        if len(a) == 0:
+            a = np.zeros(1, np.int64)  # a non-NULL pointer with n_allow = 0
+            return a.ctypes.data, 0, a
+        return a.ctypes.data, len(a), a
+
+    def search_exact_batch(self, Q, k, allow=None):
+        """(ids [nq][k], dists [nq][k], counts [nq]); past counts[q]: id -1, distance +inf."""
+        Q = np.ascontiguousarray(Q, np.float32).reshape(-1, self.dim)
+        ids = np.empty((len(Q), k), np.int64)
+        ds = np.empty((len(Q), k), np.float32)
+        cnt = np.empty(len(Q), np.int32)
+        ap, na, _keep = self._allow(allow)
+        if self.L.mn_hnsw_search_exact_batch(self.h, Q, len(Q), k, ap, na, ids, ds, cnt) != 0:
+            raise MuninnHipError(_err())
+        return ids, ds, cnt
+
+    def search_exact(self, q, k, allow=None):
+        ids, ds, cnt = self.search_exact_batch(np.ascontiguousarray(q, np.float32).reshape(1, self.dim), k, allow)
+        return ids[0, :cnt[0]], ds[0, :cnt[0]]
+
+    def search_exact_batch_dev(self, d_q, nq, k, d_ids, d_dists, d_counts, allow=None):
+        """queries and outputs in device memory (dev_malloc); returns once the kernels have finished."""
+        ap, na, _keep = self._allow(allow)
+        if self.L.mn_hnsw_search_exact_batch_dev(self.h, d_q, nq, k, ap, na, d_ids, d_dists, d_counts) != 0:
+            raise MuninnHipError(_err())
+
+    def last_exact(self):
+        s = ExactStats()
+        if self.L.mn_hnsw_last_exact(self.h, C.byref(s)) != 0:
+            raise MuninnHipError(_err())
+        return {n: getattr(s, n) for n, _ in ExactStats._fields_}
 
     def delete(self, id) -> int:
         return self.L.mn_hnsw_delete(self.h, int(id))
