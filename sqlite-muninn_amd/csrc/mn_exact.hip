@@ -127,7 +127,11 @@ DEVI float ex_lower_bound(float A, float2 qc, float2 xc, float uc, float fl2) {
     float lb;
     if (METRIC == 0) {
         const float s = __fsub_rn(__fadd_rn(qc.x, xc.x), __fmul_rn(2.0f, A));
-        lb = s > 0.0f ? fmaxf(__fsub_rn(__fmul_rn(s, fl2), uc), 0.0f) : 0.0f; // (a sum of squares is never negative)
+        // s not finite (a_q + a_x or 2A overflows, in either direction; NaN) says nothing about d: a_q + a_x above FLT_MAX leaves
+        // d = D - ... anywhere above a_q + a_x - FLT_MAX, finite for near-collinear q and x.  No bound: 0 (a sum of squares is never
+        // negative), the row stays a candidate.  (+inf would also never pass `lb < thr` while a list is still filling, thr = +inf,
+        // and a list short of K' counts as holding every live row.)
+        lb = (s > 0.0f && s < __builtin_inff()) ? fmaxf(__fsub_rn(__fmul_rn(s, fl2), uc), 0.0f) : 0.0f;
         return lb;
     }
     const float t = fmaf(qc.x, xc.x, uc); // >= |dot_ref - A|

@@ -11,24 +11,31 @@ from util import gauss, same_bits
 
 pytestmark = pytest.mark.gpu
 
-N, NQ = 2300, 140  # two row chunks with a ragged last 128-row tile; two query tiles, the second ragged
+N, NQ = 2300, 140  # three row chunks of 768 rows (ex_chunks), the last ending in a ragged 128-row tile; two query tiles, the second ragged
 KS = (1, 10, 32, 33, 128)  # 32 / 33: the last k the matrix-core pass serves and the first it does not
 CONFIGS = [(m, d, o) for m in ("l2", "cosine", "inner_product") for d, o in
            ((4, 0), (33, 0), (128, 0), (128, 1), (200, 0), (768, 0), (768, 1))]
 PATHS = ({}, {"MN_EXACT": "valu"}, {"MN_EXACT_SLACK": "0"})
 
 
-def reference(orc, metric, order, X, ids, live, Q, k):
-    """(ids [nq][k], dists [nq][k], counts [nq]) from the oracle's distances over the slots in `live` (ascending)."""
+def distances(orc, metric, order, X, Q):
+    """[nq][n] the oracle's distance of every query to every row, in the index's order"""
+    return np.stack([orc.dist_batch(metric, q, X, order) for q in Q])
+
+
+def reference(orc, metric, order, X, ids, live, Q, k, D=None):
+    """(ids [nq][k], dists [nq][k], counts [nq]) from the oracle's distances over the slots in `live` (ascending).
+    D: distances(orc, metric, order, X, Q) where a caller ranks the same pairs more than once (a row's distance does not depend
+    on the other rows of the call)."""
     nq = len(Q)
     ri = np.full((nq, k), -1, np.int64)
     rd = np.full((nq, k), np.inf, np.float32)
     rc = np.full(nq, min(k, len(live)), np.int32)
     if len(live) == 0:
         return ri, rd, rc
-    Xl = np.ascontiguousarray(X[live])
+    Xl = np.ascontiguousarray(X[live]) if D is None else None
     for i in range(nq):
-        d = orc.dist_batch(metric, Q[i], Xl, order)
+        d = orc.dist_batch(metric, Q[i], Xl, order) if D is None else D[i][live]
         o = np.lexsort((live, d))[:k]
         ri[i, :len(o)] = ids[live[o]]
         rd[i, :len(o)] = d[o]

@@ -3,7 +3,10 @@
 taken in blocks of 12, 8, 4, 2, 1, then chains, then a dim % 4 tail), the fp16 shadow filter (ld >= 192, ld % 64 == 0) and the
 lone-search / lone-insert kernels' per-wavefront LDS tile (4 rows, 2 rows or none, by what fits the device's opt-in LDS).  Each
 entry of DIMS reaches a stated combination; the tests check every kernel family against the CPU oracle at those row lengths,
-bit for bit (ids, distance bits, counts, graphs) — and the geometry each entry claims is asserted from MN_LAT_DEBUG, not assumed."""
+bit for bit (ids, distance bits, counts, graphs) — and the geometry each entry claims is asserted from MN_LAT_DEBUG, not assumed.
+Family (f) is the exact search (csrc/mn_exact.hip): k_exact_rescore<ORDER, NCH> and k_exact_valu<ORDER, NCH> at every NCH in both
+orders, the re-score's two launch shapes (4 queries per workgroup while 16·ld bytes fit 32 KB, one above: ld > 2048) and
+k_exact_mfma's partial last 32-float stage (ld % 32 != 0)."""
 import os
 import subprocess
 import sys
@@ -11,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+from test_exact_search import check, distances, exact, reference
 from util import check_topk_f64, gauss, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,6 +50,9 @@ BUILD_DIMS = [255, 300, 708, 1024, 1283, 1536, 1999, 2050]
 # brute force: k_bruteforce (MN_BRUTE=valu) at every NCH, k_brute_mfma at rows that are not whole 32-float column tiles
 BRUTE_VALU_DIMS = [192, 300, 708, 1024, 1536, 2048, 3072]
 BRUTE_MFMA_DIMS = [226, 345, 953, 1283, 2050]
+# family (f): NCH 1, 2, 3, 4, 6, 8, 8, 0, 0; ld 228, 348, 708, 1284 and 2052 are not whole 32-float stages of k_exact_mfma; 2048 is the
+# last row re-scored 4 queries per workgroup, 2050 the first re-scored one per workgroup
+EXACT_DIMS = [226, 345, 708, 1021, 1283, 1999, 2048, 2050, 4096]
 
 
 def _ld(dim):
@@ -77,6 +84,10 @@ def test_table_states_what_the_dispatch_picks_and_reaches_every_path():
     assert {DIMS[d][4] for d in BUILD_DIMS} == {0, 2, 4} and {DIMS[d][5] for d in BUILD_DIMS} == {0, 2, 4}
     assert {DIMS[d][0] for d in BRUTE_VALU_DIMS} == {0, 1, 2, 3, 4, 6, 8}
     assert all(_ld(d) % 32 for d in BRUTE_MFMA_DIMS)
+    assert {DIMS[d][0] for d in EXACT_DIMS} == {0, 1, 2, 3, 4, 6, 8}
+    assert any(_ld(d) % 32 != 0 for d in EXACT_DIMS)
+    assert {_ld(d) * 16 <= 32768 for d in EXACT_DIMS} == {True, False}
+    assert _ld(2048) * 16 == 32768 and 2050 in EXACT_DIMS  # both sides of the re-score's switch, at the switch
 
 
 def _orders(gpu, orc):
@@ -321,6 +332,47 @@ def test_bruteforce_valu_against_f64(gpu, monkeypatch, dim):
 def test_bruteforce_mfma_against_f64(gpu, monkeypatch, dim):
     for metric in METRICS:
         _brute(gpu, dim, metric, gpu.ORDER_SSE, 140, 16, False, monkeypatch)
+
+
+# ───────────────────────── (f) exact search ─────────────────────────
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", EXACT_DIMS)
+def test_exact_search(gpu, orc, monkeypatch, dim):
+    """candidate pass + re-score (default), the walk forced (MN_EXACT=valu) and the walk by k (33 > 32): the oracle's k nearest
+    live rows under (d, slot), ids and distance bits, for every metric in both orders"""
+    n, nq = 300, 40  # two full 128-row tiles and a ragged one
+    X = gauss(n, dim, 120 + dim)
+    X[17] = X[3]  # exact duplicate rows: the lower slot comes first
+    X[5] = 0.0
+    Q = gauss(nq, dim, 121 + dim)
+    Q[0] = X[3]
+    ids = np.arange(100, 100 + n, dtype=np.int64)
+    for metric in METRICS:
+        for tag, go, oo in _orders(gpu, orc):
+            D = distances(orc, metric, oo, X, Q)
+            top1 = int(np.argmin(D[1]))  # a would-be top-1 goes
+            assert top1 not in (3, 17), (metric, tag)
+            dead = sorted({top1, 40, 290, 150} - {3, 17}, key=lambda s: s != top1)[:3]
+            assert len(dead) == 3 and top1 in dead
+            g = gpu.HnswIndex(dim, metric, 8, 32, order=go)
+            assert g.insert_batch(ids, X, gpu.BUILD_BATCHED) == 0
+            for d in dead:
+                assert g.delete(int(ids[d])) == 0
+            live = np.setdiff1d(np.arange(n), dead)
+            for k, env in ((10, {}), (10, {"MN_EXACT": "valu"}), (33, {})):
+                key = (metric, tag, k, env)
+                want = reference(orc, metric, oo, X, ids, live, Q, k, D)
+                assert ids[top1] not in want[0][1], key
+                assert metric == "inner_product" or list(want[0][0][:2]) == [103, 117], key
+                for name, v in env.items():
+                    monkeypatch.setenv(name, v)
+                got, st = exact(g, Q, k)
+                for name in env:
+                    monkeypatch.delenv(name)
+                check(got, want, key)
+                assert st["n_mfma_queries"] == (nq if k <= 32 and not env else 0), (key, st)
+            g.close()
 
 
 # ───────────────────────── the dimension ceiling ─────────────────────────
