@@ -264,6 +264,24 @@ int mn_hnsw_search_exact_batch_dev(mn_index *idx, const float *d_queries, int64_
  * row touched: always 0); kernel_ms = HIP-event time of the call's kernels. */
 int mn_hnsw_last_exact(mn_index *idx, mn_exact_stats *out);
 
+/* ---- exact k-NN graph of the index's own rows (the self-join) ----
+ * The reference's entity-resolution pipeline (src/llama_er.c:207-286) asks every row of an hnsw_index for its k + 1 nearest rows,
+ * one SELECT and one MATCH per row, and keeps the pairs under a distance threshold.  This call gives the exact answer to that loop
+ * without a vector leaving the device.  Slots are 0 .. mn_hnsw_slot_count() - 1 in insertion order; a deleted row keeps its slot.
+ * For a live slot s the answer is the k smallest rows under (d ascending as floats, slot ascending) among the live slots t != s
+ * with d <= max_distance, where d = the bits mn_vec_dist_batch gives for the index's metric and order with row s's stored vector
+ * as the query.  The exclusion is by slot: a duplicate of row s is a neighbour like any other.  1 <= k <= 128; max_distance = +inf
+ * means no cut, NaN is an argument error.
+ * Outputs are indexed by slot: out_ids [slot_count][k] (ids, not slots), out_dists [slot_count][k], out_counts [slot_count];
+ * counts[s] = -1 for a deleted slot (its ids -1, distances +inf), else the neighbours kept (0..k); past counts[s]: id -1, +inf.
+ * An index without slots answers nothing and returns 0.  The index, its graph and its shadow are left as they were.
+ * The slots go through as query batches of MN_KNN_BATCH rows (default 16384, rounded up to a multiple of 128, read per call); each
+ * batch takes mn_hnsw_search_exact_batch's passes with the row store as both operands, and MN_EXACT / MN_EXACT_SLACK mean what
+ * they mean there.  mn_hnsw_last_exact reports the call summed over its batches: n_queries = the live rows asked. */
+int mn_hnsw_knn_graph(mn_index *idx, int k, float max_distance, int64_t *out_ids, float *out_dists, int *out_counts);
+/* outputs in device memory on idx's device; returns once the kernels have finished */
+int mn_hnsw_knn_graph_dev(mn_index *idx, int k, float max_distance, int64_t *d_out_ids, float *d_out_dists, int *d_out_counts);
+
 /* ---- graph_csr.h / graph_community.c replacements (a18-a22) ---- */
 typedef struct mn_graph mn_graph; /* device-resident adjacency: GraphData.out / .in (src/graph_load.h:27-37) as two
                                      CsrArray (src/graph_csr.h:27-34: int32 offsets[V+1], int32 targets[E], f64 weights[E]|NULL) */

@@ -172,6 +172,15 @@ size_t mn_exact_valu_lds_bytes(int ld);
 int mn_launch_exact_valu(const MnDevIndex &ix, const float *d_queries, const int *d_qsel, long long n, int k, const unsigned *d_allow,
                          long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
 void mn_launch_exact_fill(long long nq, int k, long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
+// The self-join flavour (mn_hnsw_knn_graph): the queries are the slots s0 .. s0 + nq - 1 of the row store itself, a
+// query never lists its own slot, only rows with d <= r are kept (r = +inf: no cut) and a deleted query slot answers count -1.
+// Outputs are the batch's own: [nq][k], [nq][k], [nq].  d_xc [n_slots]: mn_launch_knn_prep_rows, once per call.  scratch:
+// mn_exact_mfma_scratch_bytes(ix, nq, kp) bytes are enough.  d_ctr and d_marked (indices within the batch) as above.
+void mn_launch_knn_prep_rows(const MnDevIndex &ix, void *d_xc, hipStream_t st);
+int mn_launch_knn_mfma(const MnDevIndex &ix, int s0, long long nq, int k, int kp, float r, const void *d_xc, void *scratch,
+                       long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr, int *d_marked, hipStream_t st);
+int mn_launch_knn_valu(const MnDevIndex &ix, int s0, const int *d_qsel, long long n, int k, float r, long long *d_out_ids,
+                       float *d_out_d, int *d_out_cnt, hipStream_t st);
 
 // sharded index (config 3): per-shard top-k lists gathered as [world][nq][k] → global top-k per query in the total order
 // (distance, shard rank, position)  (mn_kernels.hip)

@@ -11,7 +11,12 @@
 //                    would belong in the answer) or when the list holds every live row.  Other queries are marked.
 //   k_exact_valu     the index's inner loop over every live row (k_bruteforce's shape, any k <= 128), with distances and the
 //                    (d, slot) tie rule: marked queries gathered into one launch, k > 32, MN_EXACT=valu.
+//
+// The same three kernels serve the self-join (mn_hnsw_knn_graph) as their SELF = true instantiations: the queries
+// are a range of slots of the row store itself (no padded copy), a query never admits its own slot, every list's threshold starts
+// at the radius and the answer is cut at d <= r.  SELF is a template parameter: the search flavour compiles without any of it.
 #include "mn_dist.hpp"
+#include <type_traits>
 
 #define EX_KMAX 128 // k_exact_valu
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -41,6 +46,22 @@ struct MnExactArgs {
     int *out_cnt;
     unsigned long long *ctr; // [0] marked queries [1] rows re-scored [2] rows whose exact distance lies below their bound
     int *marked;             // [nq] indices of the marked queries, ctr[0] of them
+};
+
+// the self-join flavour: query q of the batch is slot s0 + q, and a.q = ix.vectors + s0 * ld
+struct MnKnnArgs : MnExactArgs {
+    int s0;     // first slot of the batch
+    float r;    // the radius: only rows with d <= r are kept (+inf: no cut)
+    float thr0; // nextafterf(r, +inf): what every list's threshold starts at (lb < thr0 is lb <= r)
+};
+template <bool SELF> struct ExArgs { typedef MnExactArgs type; };
+template <> struct ExArgs<true> { typedef MnKnnArgs type; };
+// k_exact_valu's last argument.  (A wrapper kernel around a shared body would keep the search's argument block as it was, but the
+// compiler then allocates the body's registers differently; an empty struct leaves the search's instruction stream bit for bit.)
+struct ExNoSelf {};
+struct ExSelf {
+    int s0;
+    float r;
 };
 
 DEVI bool ex_row_ok(const MnDevIndex &ix, const unsigned *allow, int row) {
@@ -88,18 +109,20 @@ __global__ void __launch_bounds__(256) k_exact_prep_rows(MnDevIndex ix, float2 *
 //   l2:     x = N (1 - 4g - 8u) rounded down
 //   ip:     x = 4g |q| (1 + 2^-20) rounded up
 //   cosine: x as ip, y = (1 + 2^-19) / sqrt(na) rounded up, na = |q|² in the index's order (+inf below 2^-40)
-template <int ORDER>
+// SELF: `queries` is the row store from the batch's first slot on, stride ld, already zero padded; no copy is made (qpad unused).
+template <int ORDER, bool SELF = false>
 __global__ void __launch_bounds__(64) k_exact_prep_q(MnDevIndex ix, const float *queries, long long nq, float *qpad, float2 *qc) {
     extern __shared__ __align__(16) unsigned char smem[];
     float *q = reinterpret_cast<float *>(smem);
     const int lane = threadIdx.x;
     const long long qi = blockIdx.x;
-    const float *src = queries + (size_t)qi * ix.dim;
+    const float *src = queries + (size_t)qi * (SELF ? ix.ld : ix.dim);
     double acc = 0.0;
     for (int i = lane; i < ix.ld; i += 64) {
-        const float v = i < ix.dim ? src[i] : 0.0f;
+        const float v = (SELF || i < ix.dim) ? src[i] : 0.0f;
         q[i] = v;
-        qpad[(size_t)qi * ix.ld + i] = v;
+        if (!SELF)
+            qpad[(size_t)qi * ix.ld + i] = v;
         acc = fma((double)v, (double)v, acc);
     }
     __syncthreads();
@@ -150,8 +173,10 @@ DEVI float ex_lower_bound(float A, float2 qc, float2 xc, float uc, float fl2) {
 // ───────────────────────── k_exact_mfma ─────────────────────────
 // The tile loop of k_brute_mfma: a workgroup (4 wavefronts) owns 128 queries and walks a chunk of the rows 128 at a time; wavefront w
 // owns queries 32w..32w+31 against all 128 rows of the tile.  Each (query tile, row chunk) writes one partial list per query.
-template <int METRIC>
-__global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, MnExactArgs a) {
+// SELF: the A operand is the row store itself (a.q = ix.vectors + s0 * ld; a query row at or beyond n_slots, q0 + row >= nq, is
+// not read), the pair (query s0 + q, row s0 + q) is never admitted, and the thresholds start at a.thr0.
+template <int METRIC, bool SELF = false>
+__global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, typename ExArgs<SELF>::type a) {
     extern __shared__ __align__(16) unsigned char smem[];
     float *As = reinterpret_cast<float *>(smem);           // [EX_KC][EX_LD]
     float *Bs = As + EX_KC * EX_LD;                        // [EX_KC][EX_LD]
@@ -169,7 +194,10 @@ __global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, MnExactArgs a
     const int r_end = r_begin + a.rows_per_chunk < ix.n_slots ? r_begin + a.rows_per_chunk : ix.n_slots;
     if (tid < EX_Q) {
         qc_s[tid] = a.qc[q0 + tid];
-        thr[tid] = __builtin_inff();
+        if constexpr (SELF)
+            thr[tid] = a.thr0;
+        else
+            thr[tid] = __builtin_inff();
         cnt[tid] = 0;
     }
     __syncthreads();
@@ -190,7 +218,10 @@ __global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, MnExactArgs a
             for (int j = 0; j < 4; j++) {
                 const int row = srow + 32 * j;
                 const bool kin = kcol < ld;
-                pa[j] = kin ? *reinterpret_cast<const float4 *>(a.q + (size_t)(q0 + row) * ld + kcol) : make_float4(0, 0, 0, 0);
+                bool qin = kin;
+                if constexpr (SELF)
+                    qin = kin && q0 + row < a.nq;
+                pa[j] = qin ? *reinterpret_cast<const float4 *>(a.q + (size_t)(q0 + row) * ld + kcol) : make_float4(0, 0, 0, 0);
                 pb[j] = (kin && rt + row < ix.n_slots)
                             ? *reinterpret_cast<const float4 *>(ix.vectors + (size_t)(rt + row) * ld + kcol)
                             : make_float4(0, 0, 0, 0);
@@ -229,7 +260,10 @@ __global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, MnExactArgs a
             for (int reg = 0; reg < 16; reg++) {
                 const int ql = 32 * w + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); // C/D map: row of the tile = query
                 const float d = ex_lower_bound<METRIC>(acc[t][reg], qc_s[ql], xc, a.uc, a.fl2);
-                unsigned long long m = __ballot(rv && q0 + ql < a.nq && d < thr[ql]);
+                bool other = true;
+                if constexpr (SELF)
+                    other = row != a.s0 + (int)q0 + ql;
+                unsigned long long m = __ballot(rv && other && q0 + ql < a.nq && d < thr[ql]);
                 while (m) {
                     const int b = __ffsll((long long)m) - 1;
                     m &= m - 1;
@@ -281,12 +315,20 @@ __global__ void __launch_bounds__(256) k_exact_mfma(MnDevIndex ix, MnExactArgs a
 
 // ───────────────────────── k_exact_rescore ─────────────────────────
 // blockDim.x / 64 wavefronts, one query each; LDS: one padded query per wavefront.
-template <int ORDER, int NCH>
-__global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, MnExactArgs a) {
+// SELF: query q is slot a.s0 + q, read from the row store.  A deleted slot answers count -1.  The sorted list is cut at the first
+// entry that fails d <= r; a full list that the cut leaves short of k cannot be certified (rows outside it have d >= cut, and
+// cut <= r: one of them may lie within the radius), so it is marked.
+template <int ORDER, int NCH, bool SELF = false>
+__global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, typename ExArgs<SELF>::type a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long q = (long long)blockIdx.x * (blockDim.x >> 6) + wv;
-    const bool live = q < a.nq;
+    bool live = q < a.nq;
+    bool dead = false;
+    if constexpr (SELF) {
+        dead = live && ix.deleted[a.s0 + q];
+        live = live && !dead;
+    }
     const int K = a.kp;
     float *qs = reinterpret_cast<float *>(smem) + (size_t)wv * ix.ld;
     // lane i holds entry i of the list: the chunks' lists (each ascending) folded in row order
@@ -326,6 +368,16 @@ __global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, MnExactArg
         }
     }
     __syncthreads();
+    if constexpr (SELF) {
+        if (dead) {
+            for (int i = lane; i < a.k; i += 64) {
+                a.out_ids[q * a.k + i] = -1;
+                a.out_d[q * a.k + i] = __builtin_inff();
+            }
+            if (lane == 0)
+                a.out_cnt[q] = -1;
+        }
+    }
     if (!live)
         return;
     const int n = c;
@@ -340,8 +392,15 @@ __global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, MnExactArg
         const int sj = __shfl(ms, j);
         rank += (dj < d || (dj == d && sj < ms)) ? 1 : 0;
     }
-    const int k = a.k, found = n < k ? n : k;
-    if (lane < n && rank < k) {
+    const int k = a.k;
+    int found = n < k ? n : k;
+    bool keep = lane < n && rank < k;
+    if constexpr (SELF) {
+        const int within = __popcll(__ballot(lane < n && d <= a.r)); // ascending order: the entries within the radius come first
+        found = within < k ? within : k;
+        keep = keep && d <= a.r;
+    }
+    if (keep) {
         a.out_ids[q * k + rank] = ix.ids[ms];
         a.out_d[q * k + rank] = d;
     }
@@ -353,6 +412,8 @@ __global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, MnExactArg
     if (!final_) { // n == K' >= k
         const unsigned long long who = __ballot(lane < n && rank == k - 1);
         final_ = who != 0 && __shfl(d, __ffsll((long long)who) - 1) < cut;
+        if constexpr (SELF)
+            final_ = final_ && found == k;
     }
     if (lane == 0) {
         a.out_cnt[q] = found;
@@ -368,9 +429,12 @@ __global__ void __launch_bounds__(256) k_exact_rescore(MnDevIndex ix, MnExactArg
 // k_bruteforce's shape (mn_brute.hip): one 256-thread workgroup per query, 4 wavefronts stride over the rows 64 at a time, each
 // keeping a sorted top-k in LDS (equal distances: the lower slot stays first — a wavefront meets its rows in slot order), wave 0
 // merges by (d, slot).  qsel: the queries to answer (null: all nq).
-template <int ORDER, int NCH>
+// SELF (SF = ExSelf): `queries` is the row store from slot sf.s0 on, stride ld; query qi is slot sf.s0 + qi, which is never
+// admitted, nor is a row with d > sf.r (so the merge ends at the cut); a deleted query slot answers count -1.
+template <int ORDER, int NCH, class SF = ExNoSelf>
 __global__ void __launch_bounds__(256) k_exact_valu(MnDevIndex ix, const float *queries, const int *qsel, int k, const unsigned *allow,
-                                                    long long *out_ids, float *out_d, int *out_cnt) {
+                                                    long long *out_ids, float *out_d, int *out_cnt, SF sf) {
+    constexpr bool SELF = std::is_same<SF, ExSelf>::value;
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int wcnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -378,9 +442,22 @@ __global__ void __launch_bounds__(256) k_exact_valu(MnDevIndex ix, const float *
     float *q = reinterpret_cast<float *>(smem);                 // [ld]
     float *topd = q + ix.ld;                                    // [4][EX_KMAX]
     int *tops = reinterpret_cast<int *>(topd + 4 * EX_KMAX);    // [4][EX_KMAX]
-    const float *qsrc = queries + (size_t)qi * ix.dim;
+    int self = -1;
+    if constexpr (SELF) {
+        self = sf.s0 + (int)qi;
+        if (ix.deleted[self]) { // (uniform over the workgroup)
+            for (int i = tid; i < k; i += 256) {
+                out_ids[qi * k + i] = -1;
+                out_d[qi * k + i] = __builtin_inff();
+            }
+            if (tid == 0)
+                out_cnt[qi] = -1;
+            return;
+        }
+    }
+    const float *qsrc = queries + (size_t)qi * (SELF ? ix.ld : ix.dim);
     for (int i = tid; i < ix.ld; i += 256)
-        q[i] = i < ix.dim ? qsrc[i] : 0.0f;
+        q[i] = (SELF || i < ix.dim) ? qsrc[i] : 0.0f;
     __syncthreads();
     float qnorm = 0.0f;
     if (ix.metric == 1)
@@ -395,7 +472,9 @@ __global__ void __launch_bounds__(256) k_exact_valu(MnDevIndex ix, const float *
         sub.norms = ix.norms ? ix.norms + base : nullptr;
         const int myslot = lane < n ? lane : 0;
         const float d = rows_distance<ORDER, NCH>(sub, q, qnorm, myslot, n, lane);
-        const bool ok = lane < n && ex_row_ok(ix, allow, base + myslot);
+        bool ok = lane < n && ex_row_ok(ix, allow, base + myslot);
+        if constexpr (SELF)
+            ok = ok && base + myslot != self && d <= sf.r;
         const float worst = cnt >= k ? myd[k - 1] : __builtin_inff();
         unsigned long long m = __ballot(ok && (cnt < k || d < worst));
         while (m) {
@@ -490,7 +569,8 @@ int mn_launch_exact_valu(const MnDevIndex &ix, const float *d_queries, const int
     const size_t lds = mn_exact_valu_lds_bytes(ix.ld);
     const dim3 grid((unsigned)n), block(256);
 #define MN_EV(O, N)                                                                                                                 \
-    hipLaunchKernelGGL((k_exact_valu<O, N>), grid, block, lds, st, ix, d_queries, d_qsel, k, d_allow, d_out_ids, d_out_d, d_out_cnt)
+    hipLaunchKernelGGL((k_exact_valu<O, N>), grid, block, lds, st, ix, d_queries, d_qsel, k, d_allow, d_out_ids, d_out_d, d_out_cnt,   \
+                       ExNoSelf())
     if (ix.order == MN_ORDER_SSE_V) {
         MN_EV(MN_ORDER_SSE_V, 0);
     } else {
@@ -531,6 +611,16 @@ size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp) {
     const size_t nq_pad = (size_t)((nq + EX_Q - 1) / EX_Q) * EX_Q;
     return ex_up(nq_pad * ix.ld * 4) + ex_up(nq_pad * 8) + ex_up((size_t)ix.n_slots * 8) + 2 * ex_up((size_t)nc * nq * kp * 4) +
            ex_up((size_t)nc * nq * 4);
+}
+
+static void ex_bound_consts(int ld, float *uc, float *fl2) {
+    // what gradual underflow can lose of either dot product (2^-150 per operation), with room to spare
+    *uc = (float)(ld + 8) * 0x1p-140f;
+    const double nu = (double)(ld + 8) * 0x1p-24, g = nu / (1.0 - nu);
+    float f = (float)(1.0 - 4.0 * g - 0x1p-20);
+    while ((double)f > 1.0 - 4.0 * g - 0x1p-20)
+        f = nextafterf(f, 0.0f);
+    *fl2 = f;
 }
 
 template <typename K> static bool ex_grant(K kern, size_t bytes) { return mn_lds_grant(reinterpret_cast<const void *>(kern), bytes); }
@@ -578,15 +668,7 @@ int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long
     a.nq = nq;
     a.k = k;
     a.kp = kp;
-    // what gradual underflow can lose of either dot product (2^-150 per operation), with room to spare
-    a.uc = (float)(ix.ld + 8) * 0x1p-140f;
-    {
-        const double nu = (double)(ix.ld + 8) * 0x1p-24, g = nu / (1.0 - nu);
-        float f = (float)(1.0 - 4.0 * g - 0x1p-20);
-        while ((double)f > 1.0 - 4.0 * g - 0x1p-20)
-            f = nextafterf(f, 0.0f);
-        a.fl2 = f;
-    }
+    ex_bound_consts(ix.ld, &a.uc, &a.fl2);
     a.out_ids = d_out_ids;
     a.out_d = d_out_d;
     a.out_cnt = d_out_cnt;
@@ -618,5 +700,121 @@ int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long
         }
     }
 #undef MN_ER
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ───────────────────────── the self-join (mn_hnsw_knn_graph) ─────────────────────────
+void mn_launch_knn_prep_rows(const MnDevIndex &ix, void *d_xc, hipStream_t st) {
+    hipLaunchKernelGGL(k_exact_prep_rows, dim3((unsigned)(((long long)ix.n_slots * 16 + 255) / 256)), dim3(256), 0, st, ix,
+                       static_cast<float2 *>(d_xc));
+}
+
+// One batch of query slots [s0, s0 + nq) through candidate pass, re-score and certificate.  The batch's scratch holds the query
+// constants [nq_pad] and the partial lists, cut as mn_launch_exact_mfma cuts them: mn_exact_mfma_scratch_bytes(ix, nq, kp) covers it.
+int mn_launch_knn_mfma(const MnDevIndex &ix, int s0, long long nq, int k, int kp, float r, const void *d_xc, void *scratch,
+                       long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr, int *d_marked, hipStream_t st) {
+    if (nq <= 0 || k <= 0 || kp < k || kp > 64 || s0 < 0 || s0 + nq > ix.n_slots || r != r)
+        return -1;
+    const size_t lds = ex_mfma_lds_bytes(kp);
+    const bool granted = ix.metric == 1   ? ex_grant(k_exact_mfma<1, true>, lds)
+                         : ix.metric == 0 ? ex_grant(k_exact_mfma<0, true>, lds)
+                                          : ex_grant(k_exact_mfma<2, true>, lds);
+    if (!granted)
+        return 1;
+    MnKnnArgs a;
+    ex_chunks(ix, nq, &a.n_chunks, &a.rows_per_chunk);
+    const long long qt = (nq + EX_Q - 1) / EX_Q;
+    const size_t nq_pad = (size_t)qt * EX_Q;
+    unsigned char *p = static_cast<unsigned char *>(scratch);
+    float2 *qc = reinterpret_cast<float2 *>(p);
+    p += ex_up(nq_pad * 8);
+    a.pd = reinterpret_cast<float *>(p);
+    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
+    a.pi = reinterpret_cast<int *>(p);
+    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
+    a.pc = reinterpret_cast<int *>(p);
+    // the padding queries of the last tile: zero constants (their rows of the tile are neither read nor looked at)
+    if (hipMemsetAsync(qc, 0, ex_up(nq_pad * 8), st) != hipSuccess)
+        return -1;
+    const float *rows = ix.vectors + (size_t)s0 * ix.ld;
+    const size_t qlds = (size_t)ix.ld * 4;
+    if (ix.order == MN_ORDER_SSE_V)
+        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_SSE_V, true>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, nullptr, qc);
+    else
+        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_WAVE_V, true>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, nullptr, qc);
+    a.q = rows;
+    a.qc = qc;
+    a.xc = static_cast<const float2 *>(d_xc);
+    a.allow = nullptr;
+    a.nq = nq;
+    a.k = k;
+    a.kp = kp;
+    ex_bound_consts(ix.ld, &a.uc, &a.fl2);
+    a.out_ids = d_out_ids;
+    a.out_d = d_out_d;
+    a.out_cnt = d_out_cnt;
+    a.ctr = d_ctr;
+    a.marked = d_marked;
+    a.s0 = s0;
+    a.r = r;
+    a.thr0 = nextafterf(r, __builtin_inff()); // lb < thr0 is lb <= r (r = +inf stays +inf)
+    const dim3 grid((unsigned)qt, (unsigned)a.n_chunks);
+    if (ix.metric == 1)
+        hipLaunchKernelGGL((k_exact_mfma<1, true>), grid, dim3(256), lds, st, ix, a);
+    else if (ix.metric == 0)
+        hipLaunchKernelGGL((k_exact_mfma<0, true>), grid, dim3(256), lds, st, ix, a);
+    else
+        hipLaunchKernelGGL((k_exact_mfma<2, true>), grid, dim3(256), lds, st, ix, a);
+    const int wpb = (size_t)ix.ld * 16 <= 32 * 1024 ? 4 : 1;
+    const dim3 rgrid((unsigned)((nq + wpb - 1) / wpb)), rblock(64 * wpb);
+    const size_t rlds = (size_t)ix.ld * 4 * wpb;
+#define MN_ER(O, N) hipLaunchKernelGGL((k_exact_rescore<O, N, true>), rgrid, rblock, rlds, st, ix, a)
+    if (ix.order == MN_ORDER_SSE_V) {
+        MN_ER(MN_ORDER_SSE_V, 0);
+    } else {
+        switch (ex_pick_nch(ix.ld)) {
+        case 1: MN_ER(MN_ORDER_WAVE_V, 1); break;
+        case 2: MN_ER(MN_ORDER_WAVE_V, 2); break;
+        case 3: MN_ER(MN_ORDER_WAVE_V, 3); break;
+        case 4: MN_ER(MN_ORDER_WAVE_V, 4); break;
+        case 6: MN_ER(MN_ORDER_WAVE_V, 6); break;
+        case 8: MN_ER(MN_ORDER_WAVE_V, 8); break;
+        default: MN_ER(MN_ORDER_WAVE_V, 0); break;
+        }
+    }
+#undef MN_ER
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the index's inner loop over every row for the batch's queries d_qsel[0..n) (null: 0..n-1), indices within the batch
+int mn_launch_knn_valu(const MnDevIndex &ix, int s0, const int *d_qsel, long long n, int k, float r, long long *d_out_ids,
+                       float *d_out_d, int *d_out_cnt, hipStream_t st) {
+    if (n <= 0)
+        return 0;
+    if (k <= 0 || k > EX_KMAX || s0 < 0 || s0 >= ix.n_slots || r != r)
+        return -1;
+    const size_t lds = mn_exact_valu_lds_bytes(ix.ld);
+    const dim3 grid((unsigned)n), block(256);
+    const float *rows = ix.vectors + (size_t)s0 * ix.ld;
+    ExSelf sf;
+    sf.s0 = s0;
+    sf.r = r;
+#define MN_EV(O, N)                                                                                                                 \
+    hipLaunchKernelGGL((k_exact_valu<O, N, ExSelf>), grid, block, lds, st, ix, rows, d_qsel, k, (const unsigned *)nullptr, d_out_ids,  \
+                       d_out_d, d_out_cnt, sf)
+    if (ix.order == MN_ORDER_SSE_V) {
+        MN_EV(MN_ORDER_SSE_V, 0);
+    } else {
+        switch (ex_pick_nch(ix.ld)) {
+        case 1: MN_EV(MN_ORDER_WAVE_V, 1); break;
+        case 2: MN_EV(MN_ORDER_WAVE_V, 2); break;
+        case 3: MN_EV(MN_ORDER_WAVE_V, 3); break;
+        case 4: MN_EV(MN_ORDER_WAVE_V, 4); break;
+        case 6: MN_EV(MN_ORDER_WAVE_V, 6); break;
+        case 8: MN_EV(MN_ORDER_WAVE_V, 8); break;
+        default: MN_EV(MN_ORDER_WAVE_V, 0); break;
+        }
+    }
+#undef MN_EV
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -2532,6 +2532,128 @@ extern "C" int mn_hnsw_search_exact_batch(mn_index *x, const float *queries, int
     return 0;
 } MN_GUARD_END(set_err, MN_NOTHING, -1)
 
+// ───────────────────────── exact k-NN graph of the index's own rows ─────────────────────────
+
+// Outputs in device memory, indexed by slot.  The slots go through in batches of B queries; per batch the rules of
+// exact_search_dev: candidate pass + certificate, the marked queries gathered into one walk; k > 32, MN_EXACT=valu and a refused
+// LDS grant walk every row.
+static int knn_graph_dev(mn_index *x, int k, float r, int64_t *d_ids, float *d_dists, int *d_counts) {
+    if (k < 1 || k > 128) {
+        set_err("mn_hnsw_knn_graph: k must be 1..128 (got %d)", k);
+        return -1;
+    }
+    if (r != r) {
+        set_err("mn_hnsw_knn_graph: max_distance is NaN");
+        return -1;
+    }
+    if (push_links(x) || sync_meta(x))
+        return -1;
+    x->last_exact = {0, 0, 0, 0, 0, 0.0f};
+    const int n = x->n_slots;
+    if (n == 0)
+        return 0;
+    int64_t n_live = 0;
+    for (int s = 0; s < n; s++)
+        n_live += x->deleted[s] ? 0 : 1;
+    hipStream_t st = x->stream;
+    const char *force = getenv("MN_EXACT");
+    const char *slack_e = getenv("MN_EXACT_SLACK");
+    const char *batch_e = getenv("MN_KNN_BATCH"); // query slots per batch, rounded up to a multiple of 128
+    int slack = slack_e ? atoi(slack_e) : 16;
+    if (slack < 0)
+        slack = 0;
+    const int kp = std::min(k + slack, 64);
+    long long B = batch_e ? atoll(batch_e) : 16384;
+    if (B < 1)
+        B = 16384;
+    B = std::min<long long>((B + 127) / 128 * 128, ((long long)n + 127) / 128 * 128);
+    bool mfma = k <= 32 && !(force && !strcmp(force, "valu"));
+    MnDevIndex v = dev_view(x);
+    // a batch's scratch: what the search asks for at nq = B (the last, shorter batch cuts its row chunks differently)
+    const long long rem = n % B;
+    const size_t b_batch = mfma ? std::max(mn_exact_mfma_scratch_bytes(v, std::min<long long>(B, n), kp),
+                                           rem ? mn_exact_mfma_scratch_bytes(v, rem, kp) : (size_t)0)
+                                : 0;
+    const size_t b_xc = mfma ? ((size_t)n * 8 + 255) & ~(size_t)255 : 0, b_marked = ((size_t)B * 4 + 255) & ~(size_t)255;
+    ExactScratch sc;
+    if (sc.b.reserve(b_batch + b_xc + b_marked + 256, false, st))
+        return -1;
+    unsigned char *p = sc.b.p + b_batch;
+    void *d_xc = p;
+    p += b_xc;
+    int *d_marked = reinterpret_cast<int *>(p);
+    p += b_marked;
+    unsigned long long *d_ctr = reinterpret_cast<unsigned long long *>(p);
+    unsigned long long tot[3] = {0, 0, 0};
+    float ms_sum = 0.0f;
+    auto fail = [&]() {
+        set_err("mn_hnsw_knn_graph: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(st);
+        return -1;
+    };
+    for (long long s0 = 0; s0 < n; s0 += B) {
+        const long long nq = std::min<long long>(B, n - s0);
+        long long *o_ids = (long long *)d_ids + (size_t)s0 * k;
+        float *o_d = d_dists + (size_t)s0 * k;
+        int *o_c = d_counts + s0;
+        HIPCHK(hipMemsetAsync(d_ctr, 0, 4 * sizeof(unsigned long long), st));
+        HIPCHK(hipEventRecord(x->ev0, st));
+        if (mfma) {
+            if (s0 == 0) // the rows' constants: once per call
+                mn_launch_knn_prep_rows(v, d_xc, st);
+            const int rc = mn_launch_knn_mfma(v, (int)s0, nq, k, kp, r, d_xc, sc.b.p, o_ids, o_d, o_c, d_ctr, d_marked, st);
+            if (rc < 0)
+                return fail();
+            if (rc == 1) { // the LDS grant is refused (before anything of the pass was launched): the whole call takes the walk
+                mfma = false;
+                tot[0] = tot[1] = tot[2] = 0;
+            }
+        }
+        if (mfma) {
+            unsigned long long ctr[3] = {0, 0, 0};
+            HIPCHK(hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (mn_launch_knn_valu(v, (int)s0, d_marked, (long long)ctr[0], k, r, o_ids, o_d, o_c, st))
+                return fail();
+            for (int i = 0; i < 3; i++)
+                tot[i] += ctr[i];
+        } else if (mn_launch_knn_valu(v, (int)s0, nullptr, nq, k, r, o_ids, o_d, o_c, st)) {
+            return fail();
+        }
+        HIPCHK(hipEventRecord(x->ev1, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, x->ev0, x->ev1) == hipSuccess)
+            ms_sum += ms;
+    }
+    x->last_exact = {n_live, mfma ? n_live : 0, (int64_t)tot[0], (int64_t)tot[1], (int64_t)tot[2], ms_sum};
+    return 0;
+}
+
+extern "C" int mn_hnsw_knn_graph_dev(mn_index *x, int k, float max_distance, int64_t *d_ids, float *d_dists, int *d_counts) try {
+    if (use_device(x))
+        return -1;
+    return knn_graph_dev(x, k, max_distance, d_ids, d_dists, d_counts);
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
+
+extern "C" int mn_hnsw_knn_graph(mn_index *x, int k, float max_distance, int64_t *out_ids, float *out_dists, int *out_counts) try {
+    if (use_device(x))
+        return -1;
+    const size_t n = (size_t)x->n_slots;
+    if (n == 0 || k < 1 || k > 128 || max_distance != max_distance)
+        return knn_graph_dev(x, k, max_distance, nullptr, nullptr, nullptr);
+    hipStream_t st = x->stream;
+    if (x->ws_outi.reserve(n * k, false, st) || x->ws_outd.reserve(n * k, false, st) || x->ws_outc.reserve(n, false, st))
+        return -1;
+    if (knn_graph_dev(x, k, max_distance, (int64_t *)x->ws_outi.p, x->ws_outd.p, x->ws_outc.p))
+        return -1;
+    HIPCHK(hipMemcpyAsync(out_ids, x->ws_outi.p, n * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_dists, x->ws_outd.p, n * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_counts, x->ws_outc.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+} MN_GUARD_END(set_err, MN_NOTHING, -1)
+
 extern "C" int mn_hnsw_last_exact(mn_index *x, mn_exact_stats *out) try {
     *out = x->last_exact;
     return 0;

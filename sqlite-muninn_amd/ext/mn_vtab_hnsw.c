@@ -27,6 +27,7 @@
 #include "mn_sqlite_abi.h"
 #include "mn_nodemap.h"
 
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -1271,6 +1272,198 @@ static sqlite3_module batch_module = {
     .xRowid = b_rowid,
 };
 
+/* ───────────────────────── hnsw_knn_graph: the exact k-NN graph of a table's own rows ─────────────────────────
+ * The reference's entity-resolution pipeline (src/llama_er.c:207-286) reads every row of an hnsw_index back, asks the graph for
+ * its k + 1 nearest rows and keeps the pairs under a distance threshold: one SELECT and one MATCH per row.  This ADDITIVE
+ * eponymous table-valued function answers that loop in one statement, exactly, without a vector leaving the device
+ * (mn_hnsw_knn_graph): for every live row its k nearest OTHER live rows, ties by insertion order, distances with the bits of the
+ * table's own metric, only those with distance <= max_distance when one is given:
+ *   SELECT src, dst, distance, rank FROM hnsw_knn_graph WHERE tbl = 'vec' AND k = 10 [AND max_distance = 0.3];
+ * src and dst are rowids, rank is 0-based; rows come ordered by (src's insertion order, rank) — an edge list graph_leiden,
+ * node2vec_train and graph_closeness take as it is. */
+typedef struct {
+    sqlite3_vtab base;
+    sqlite3 *db;
+} KnnVtab;
+typedef struct {
+    sqlite3_vtab_cursor base;
+    int64_t *src; /* [n] rowid of every slot */
+    int64_t *ids; /* [n][k] */
+    float *dists; /* [n][k] */
+    int *counts;  /* [n], -1: a deleted slot */
+    int n, k, si, ri;
+} KnnCur;
+enum { KC_SRC = 0, KC_DST, KC_DIST, KC_RANK, KC_TBL, KC_K, KC_MAXD };
+
+static int k_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
+    (void)aux; (void)argc; (void)argv; (void)err;
+    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(src INTEGER, dst INTEGER, distance REAL, rank INTEGER, tbl TEXT HIDDEN,"
+                                      " k INTEGER HIDDEN, max_distance REAL HIDDEN)");
+    if (rc != SQLITE_OK)
+        return rc;
+    KnnVtab *v = (KnnVtab *)sqlite3_malloc((int)sizeof(KnnVtab));
+    if (!v)
+        return SQLITE_NOMEM;
+    memset(v, 0, sizeof(*v));
+    v->db = db;
+    *out = &v->base;
+    return SQLITE_OK;
+}
+static int k_disconnect(sqlite3_vtab *v) {
+    sqlite3_free(v);
+    return SQLITE_OK;
+}
+static int k_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
+    (void)v;
+    int which[3] = {-1, -1, -1};
+    for (int i = 0; i < ii->nConstraint; i++) {
+        if (!ii->aConstraint[i].usable || ii->aConstraint[i].op != SQLITE_INDEX_CONSTRAINT_EQ)
+            continue;
+        int col = ii->aConstraint[i].iColumn;
+        if (col >= KC_TBL && col <= KC_MAXD)
+            which[col - KC_TBL] = i;
+    }
+    int arg = 1, mask = 0;
+    for (int j = 0; j < 3; j++)
+        if (which[j] >= 0) {
+            ii->aConstraintUsage[which[j]].argvIndex = arg++;
+            ii->aConstraintUsage[which[j]].omit = 1;
+            mask |= 1 << j;
+        }
+    ii->idxNum = mask;
+    ii->estimatedCost = (mask & 0x3) == 0x3 ? 100.0 : 1e12;
+    return SQLITE_OK;
+}
+static int k_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
+    (void)v;
+    KnnCur *c = (KnnCur *)calloc(1, sizeof(KnnCur));
+    if (!c)
+        return SQLITE_NOMEM;
+    *out = &c->base;
+    return SQLITE_OK;
+}
+static void k_clear(KnnCur *c) {
+    free(c->src);
+    free(c->ids);
+    free(c->dists);
+    free(c->counts);
+    c->src = 0;
+    c->ids = 0;
+    c->dists = 0;
+    c->counts = 0;
+    c->n = 0;
+}
+static int k_close(sqlite3_vtab_cursor *cur) {
+    k_clear((KnnCur *)cur);
+    free(cur);
+    return SQLITE_OK;
+}
+static void k_skip_empty(KnnCur *c) {
+    while (c->si < c->n && c->ri >= c->counts[c->si]) {
+        c->si++;
+        c->ri = 0;
+    }
+}
+static int k_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
+    (void)idxStr;
+    KnnCur *c = (KnnCur *)cur;
+    KnnVtab *kv = (KnnVtab *)cur->pVtab;
+    k_clear(c);
+    c->si = c->ri = 0;
+    if ((idxNum & 0x3) != 0x3 || argc < 2)
+        return SQLITE_OK;
+    const char *tbl = (const char *)sqlite3_value_text(argv[0]);
+    const int k = sqlite3_value_int(argv[1]);
+    const int has_r = (idxNum & 0x4) && argc >= 3 && sqlite3_value_type(argv[2]) != SQLITE_NULL;
+    const float r = has_r ? (float)sqlite3_value_double(argv[2]) : INFINITY;
+    VtabHnsw *v = tbl ? live_find(kv->db, tbl) : 0;
+    if (!v && tbl) { /* not connected yet on this connection: touching the table connects it */
+        char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", tbl);
+        sqlite3_exec(kv->db, sql, 0, 0, 0);
+        sqlite3_free(sql);
+        v = live_find(kv->db, tbl);
+    }
+    if (!v) {
+        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: no hnsw_index table named '%s'", tbl ? tbl : "");
+        return SQLITE_ERROR;
+    }
+    if (flush_pending(v) != SQLITE_OK) {
+        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
+        return SQLITE_ERROR;
+    }
+    const int n = mn_hnsw_slot_count(v->index);
+    if (n <= 0 || k < 1 || k > 128) { /* an empty table answers nothing; a k out of range is the library's error to word */
+        if (mn_hnsw_knn_graph(v->index, k, r, 0, 0, 0) != 0) {
+            kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", mn_last_error());
+            return SQLITE_ERROR;
+        }
+        return SQLITE_OK;
+    }
+    c->src = (int64_t *)malloc((size_t)n * sizeof(int64_t));
+    c->ids = (int64_t *)malloc((size_t)n * k * sizeof(int64_t));
+    c->dists = (float *)malloc((size_t)n * k * sizeof(float));
+    c->counts = (int *)malloc((size_t)n * sizeof(int));
+    int *scratch = (int *)malloc((size_t)n * 2 * sizeof(int)); /* levels and deleted flags: not needed, counts say which slots live */
+    if (!c->src || !c->ids || !c->dists || !c->counts || !scratch) {
+        free(scratch);
+        return SQLITE_NOMEM;
+    }
+    int rc = mn_hnsw_export_nodes(v->index, c->src, scratch, scratch + n);
+    free(scratch);
+    if (rc == 0)
+        rc = mn_hnsw_knn_graph(v->index, k, r, c->ids, c->dists, c->counts);
+    if (rc != 0) {
+        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", mn_last_error());
+        return SQLITE_ERROR;
+    }
+    c->n = n;
+    c->k = k;
+    k_skip_empty(c);
+    return SQLITE_OK;
+}
+static int k_next(sqlite3_vtab_cursor *cur) {
+    KnnCur *c = (KnnCur *)cur;
+    c->ri++;
+    k_skip_empty(c);
+    return SQLITE_OK;
+}
+static int k_eof(sqlite3_vtab_cursor *cur) {
+    KnnCur *c = (KnnCur *)cur;
+    return c->si >= c->n;
+}
+static int k_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
+    KnnCur *c = (KnnCur *)cur;
+    size_t at = (size_t)c->si * c->k + c->ri;
+    switch (col) {
+    case KC_SRC: sqlite3_result_int64(ctx, c->src[c->si]); break;
+    case KC_DST: sqlite3_result_int64(ctx, c->ids[at]); break;
+    case KC_DIST: sqlite3_result_double(ctx, (double)c->dists[at]); break;
+    case KC_RANK: sqlite3_result_int(ctx, c->ri); break;
+    default: sqlite3_result_null(ctx); break;
+    }
+    return SQLITE_OK;
+}
+static int k_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
+    KnnCur *c = (KnnCur *)cur;
+    *out = (sqlite3_int64)c->si * c->k + c->ri;
+    return SQLITE_OK;
+}
+static sqlite3_module knn_module = {
+    .iVersion = 0,
+    .xCreate = 0,
+    .xConnect = k_connect,
+    .xBestIndex = k_best_index,
+    .xDisconnect = k_disconnect,
+    .xDestroy = k_disconnect,
+    .xOpen = k_open,
+    .xClose = k_close,
+    .xFilter = k_filter,
+    .xNext = k_next,
+    .xEof = k_eof,
+    .xColumn = k_column,
+    .xRowid = k_rowid,
+};
+
 /* node2vec_train's output step (src/node2vec.c:540-583: INSERT every embedding into the output table) when that table is a
  * live hnsw_index of this connection in fast mode and still empty: the embeddings are trained, normalised and built into the
  * index without leaving HBM (mn_node2vec_train_into) — no per-row INSERT, no second upload — and the shadow tables are written
@@ -1341,5 +1534,7 @@ int mn_register_hnsw_module(sqlite3 *db) {
         rc = sqlite3_create_module(db, "hnsw_search_batch", &batch_module, 0); /* additive batch surface */
     if (rc == SQLITE_OK)
         rc = sqlite3_create_module(db, "hnsw_search_exact", &batch_module, (void *)&batch_module); /* non-NULL aux: the exact flavour */
+    if (rc == SQLITE_OK)
+        rc = sqlite3_create_module(db, "hnsw_knn_graph", &knn_module, 0); /* additive: the self-join of the exact search */
     return rc;
 }

@@ -107,6 +107,8 @@ SYMBOLS = [
     ("mn_hnsw_search_exact_batch_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mn_hnsw_last_exact", C.c_int, [C.c_void_p, C.POINTER(ExactStats)]),
+    ("mn_hnsw_knn_graph", C.c_int, [C.c_void_p, C.c_int, C.c_float, _i64p, _f32p, _i32p]),
+    ("mn_hnsw_knn_graph_dev", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     # multi-GPU
     ("mn_comm_unique_id", C.c_int, [C.c_void_p]),
     ("mn_comm_init_rccl", C.c_void_p, [C.c_int, C.c_int, C.c_void_p, C.c_int]),
@@ -354,6 +356,45 @@ class HnswIndex:
         if self.L.mn_hnsw_last_exact(self.h, C.byref(s)) != 0:
             raise MuninnHipError(_err())
         return {n: getattr(s, n) for n, _ in ExactStats._fields_}
+
+    # ---- exact k-NN graph of the index's own rows: every live row's k nearest other live rows, no vector leaving the device ----
+    @staticmethod
+    def _radius(max_distance):
+        return float("inf") if max_distance is None else float(max_distance)
+
+    def knn_graph_slots(self, k, max_distance=None):
+        """mn_hnsw_knn_graph as it answers: (nbr_ids [slot_count][k], dists [slot_count][k], counts [slot_count]) by slot;
+        a deleted slot has count -1.  last_exact() reports the call."""
+        n = self.slot_count
+        ids = np.empty((n, max(k, 0)), np.int64)
+        ds = np.empty((n, max(k, 0)), np.float32)
+        cnt = np.empty(n, np.int32)
+        if self.L.mn_hnsw_knn_graph(self.h, k, self._radius(max_distance), ids, ds, cnt) != 0:
+            raise MuninnHipError(_err())
+        return ids, ds, cnt
+
+    def knn_graph(self, k, max_distance=None):
+        """(ids [n_live], nbr_ids [n_live][k], dists [n_live][k], counts [n_live]): the live rows in insertion order, each with its
+        k nearest other live rows under (distance, insertion order), only those with distance <= max_distance (None: no cut);
+        past counts[i]: id -1, distance +inf."""
+        nbr, ds, cnt = self.knn_graph_slots(k, max_distance)
+        ids, _, dl = self.export_nodes()
+        live = dl == 0
+        return ids[live], nbr[live], ds[live], cnt[live]
+
+    def knn_edges(self, k, max_distance=None):
+        """The same graph as a flat edge list (src, dst, dist, rank), rank 0-based, ordered by (insertion order of src, rank):
+        what graph_leiden, node2vec_train and graph_closeness take as it is."""
+        ids, nbr, ds, cnt = self.knn_graph(k, max_distance)
+        rank = np.broadcast_to(np.arange(k, dtype=np.int32), nbr.shape)
+        keep = rank < cnt[:, None]
+        src = np.broadcast_to(ids[:, None], nbr.shape)
+        return src[keep], nbr[keep], ds[keep], rank[keep]
+
+    def knn_graph_dev(self, k, d_ids, d_dists, d_counts, max_distance=None):
+        """outputs in device memory (dev_malloc), indexed by slot: [slot_count][k], [slot_count][k], [slot_count]."""
+        if self.L.mn_hnsw_knn_graph_dev(self.h, k, self._radius(max_distance), d_ids, d_dists, d_counts) != 0:
+            raise MuninnHipError(_err())
 
     def delete(self, id) -> int:
         return self.L.mn_hnsw_delete(self.h, int(id))

@@ -1,0 +1,160 @@
+"""hnsw_knn_graph, the SQL face of the exact k-NN graph (ext/mn_vtab_hnsw.c), and the two C-ABI symbols behind it.
+The tests without the gpu mark run where no device exists: registration, schema, an error raised before any device call,
+and the exported symbols."""
+import os
+import sqlite3
+import subprocess
+
+import numpy as np
+import pytest
+
+from util import gauss, same_bits
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXT_DIR = os.path.join(ROOT, "sqlite-muninn_amd", "ext")
+EXT = os.path.join(EXT_DIR, "muninn")
+NEW_SYMBOLS = ("mn_hnsw_knn_graph", "mn_hnsw_knn_graph_dev")
+
+
+def connect(mn):
+    mn.build()
+    subprocess.run(["make", "-s", "-C", EXT_DIR], check=True)
+    c = sqlite3.connect(":memory:")
+    c.enable_load_extension(True)
+    c.load_extension(EXT)
+    return c
+
+
+@pytest.fixture
+def cpu_conn(mn):
+    """The extension loaded where no device exists: only statements that end before any device call may run here."""
+    c = connect(mn)
+    yield c
+    c.close()
+
+
+# ───────────────────────── CPU ─────────────────────────
+
+def test_module_registered(cpu_conn):
+    names = {r[0] for r in cpu_conn.execute("SELECT name FROM pragma_module_list")}
+    assert {"hnsw_knn_graph", "hnsw_search_exact", "hnsw_search_batch", "hnsw_index"} <= names
+
+
+def test_schema(cpu_conn):
+    cols = cpu_conn.execute("SELECT name, type, hidden FROM pragma_table_xinfo('hnsw_knn_graph')").fetchall()
+    assert cols == [("src", "INTEGER", 0), ("dst", "INTEGER", 0), ("distance", "REAL", 0), ("rank", "INTEGER", 0),
+                    ("tbl", "TEXT", 1), ("k", "INTEGER", 1), ("max_distance", "REAL", 1)]
+
+
+def test_unknown_table_fails_before_any_device_call(cpu_conn):
+    for sql in ("SELECT * FROM hnsw_knn_graph WHERE tbl='nope' AND k=5",
+                "SELECT * FROM hnsw_knn_graph WHERE tbl='nope' AND k=5 AND max_distance=0.5"):
+        with pytest.raises(sqlite3.OperationalError) as ei:
+            cpu_conn.execute(sql).fetchall()
+        assert str(ei.value) == "hnsw_knn_graph: no hnsw_index table named 'nope'"
+
+
+def test_no_rows_without_arguments(cpu_conn):
+    assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph").fetchall() == []
+    assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE k=5").fetchall() == []
+    assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE tbl='nope'").fetchall() == []
+
+
+def test_library_exports_the_entry_points(mn):
+    lib = mn.build()
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert set(NEW_SYMBOLS) <= exported
+    bound = {s[0] for s in mn.hnsw.SYMBOLS}
+    assert set(NEW_SYMBOLS) <= bound
+    L = mn.lib()
+    for name in NEW_SYMBOLS:
+        assert getattr(L, name).argtypes is not None
+    assert L.mn_abi_version() == 2
+
+
+# ───────────────────────── GPU ─────────────────────────
+
+SQL = "SELECT src, dst, distance, rank FROM hnsw_knn_graph WHERE tbl='kv' AND k=?"
+
+
+def same_edges(rows, edges):
+    src, dst, dist, rank = edges
+    assert [r[0] for r in rows] == src.tolist() and [r[1] for r in rows] == dst.tolist()
+    assert [r[3] for r in rows] == rank.tolist()
+    assert same_bits(np.array([r[2] for r in rows], np.float32), dist)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["exact", "deferred", "fast"])
+def test_tvf_equals_knn_edges(mn, gpu, monkeypatch, mode):
+    """In deferred and fast mode the rows are still queued when the function is called: it flushes them before it reads."""
+    monkeypatch.setenv("MUNINN_HNSW_MODE", mode)
+    c = connect(mn)
+    c.isolation_level = None
+    n, dim, k = 300, 32, 10
+    X = gauss(n, dim, 81)
+    X[40] = X[12]
+    ids = np.arange(1, n + 1, dtype=np.int64) * 3
+    c.execute(f"CREATE VIRTUAL TABLE kv USING hnsw_index(dimensions={dim}, metric='cosine', m=8, ef_construction=60)")
+    g = gpu.HnswIndex(dim, "cosine", 8, 60)
+    c.execute("BEGIN")
+    for i in range(n):
+        c.execute("INSERT INTO kv (rowid, vector) VALUES (?, ?)", (int(ids[i]), X[i].tobytes()))
+        assert g.insert(int(ids[i]), X[i]) == 0
+    want = g.knn_edges(k)
+    assert len(want[0]) == n * k
+    same_edges(c.execute(SQL, (k,)).fetchall(), want)  # inside the open transaction
+    c.execute("COMMIT")
+    same_edges(c.execute(SQL, (k,)).fetchall(), want)
+    r = float(np.median(g.knn_graph(k)[2][:, k - 1]))
+    want_r = g.knn_edges(k, r)
+    assert 0 < len(want_r[0]) < n * k
+    same_edges(c.execute(SQL + " AND max_distance=?", (k, r)).fetchall(), want_r)
+    same_edges(c.execute(SQL + " AND max_distance=?", (k, None)).fetchall(), want)  # NULL: no cut
+    assert c.execute(SQL + " AND max_distance=?", (k, -1.0)).fetchall() == []
+    c.execute("DELETE FROM kv WHERE rowid = ?", (int(ids[12]),))
+    assert g.delete(int(ids[12])) == 0
+    after = g.knn_edges(k)
+    assert int(ids[12]) not in after[0] and int(ids[12]) not in after[1] and len(after[0]) == (n - 1) * k
+    same_edges(c.execute(SQL, (k,)).fetchall(), after)
+    for bad in (0, 129):
+        with pytest.raises(sqlite3.OperationalError, match=r"^hnsw_knn_graph: mn_hnsw_knn_graph: k must be 1\.\.128"):
+            c.execute(SQL, (bad,)).fetchall()
+    with pytest.raises(sqlite3.OperationalError, match="hnsw_knn_graph: no hnsw_index table named 'nope'"):
+        c.execute(SQL.replace("'kv'", "'nope'"), (k,)).fetchall()
+    g.close()
+    c.close()
+
+
+@pytest.mark.gpu
+def test_knn_graph_into_leiden(mn, gpu, orc):
+    """The two halves of the repository in one statement sequence: the exact k-NN graph of two well separated blobs is an edge
+    table graph_leiden takes as it is; no edge and no community crosses the blobs."""
+    per, dim, k = 150, 16, 8
+    centre = np.zeros(dim, np.float32)
+    centre[0] = 10.0  # 10 sigma apart
+    X = gauss(2 * per, dim, 91)
+    blob = np.arange(2 * per) % 2  # interleaved: the blobs share no slot range
+    X[blob == 1] += centre
+    # the claim, on the oracle's distances first: every row's 8 nearest other rows lie in its own blob
+    for i in range(2 * per):
+        d = orc.dist_batch("l2", X[i], X, 0)
+        d[i] = np.inf
+        assert (blob[np.argsort(d, kind="stable")[:k]] == blob[i]).all(), i
+    c = connect(mn)
+    c.execute(f"CREATE VIRTUAL TABLE v USING hnsw_index(dimensions={dim}, metric='l2', m=8)")
+    with c:
+        for i in range(2 * per):
+            c.execute("INSERT INTO v (rowid, vector) VALUES (?, ?)", (i + 1, X[i].tobytes()))
+    c.execute("CREATE TABLE e AS SELECT src, dst FROM hnsw_knn_graph WHERE tbl='v' AND k=8")
+    edges = c.execute("SELECT src, dst FROM e").fetchall()
+    assert len(edges) == 2 * per * k
+    assert all(blob[s - 1] == blob[d - 1] for s, d in edges)
+    rows = c.execute("SELECT node, community_id FROM graph_leiden WHERE edge_table='e' AND src_col='src' AND dst_col='dst'").fetchall()
+    assert sorted(int(r[0]) for r in rows) == list(range(1, 2 * per + 1))
+    members = {}
+    for node, com in rows:
+        members.setdefault(com, set()).add(int(blob[int(node) - 1]))
+    assert len(members) >= 2 and all(len(b) == 1 for b in members.values()), members
+    c.close()
