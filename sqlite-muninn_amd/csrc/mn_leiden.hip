@@ -568,7 +568,7 @@ struct LeiArgs {
     const long long *bigoff;     // [biglist index] offset of the node's region in scratch_c/w/e (nodes with more than LEI_CAP edges)
     int big0, big1;              // the slice of biglist inside [b0, b1)
     int parity;                  // round parity: out[1 + parity] counts this round's safe winners
-    int big_log2h;               // hash table size of a wide node (unweighted): 2^big_log2h >= 2 * lds_cap
+    int big_log2h;               // table size of a wide node: 2^big_log2h >= lds_cap (one entry per edge at most, so it may fill up)
     int sync;                    // 1: whole-graph synchronous sweep — every positive-gain mover applies, no tallies (k_leiden_apply_sync)
     int pickless;                // this sweep only allows moves to a community with a smaller id
     int sg_log2h;                // log2 of a sub-group's table size (unweighted): LEI_SG_LOG2H, or one less once labels have merged
