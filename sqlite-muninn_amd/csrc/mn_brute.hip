@@ -8,6 +8,7 @@
 //   k_bruteforce   VALU kernel using the index's own inner loop (any k <= 128); one 256-thread workgroup per query:
 //                  4 wavefronts stride over the rows, each keeping a sorted top-k in LDS; wave 0 merges.
 #include "mn_dist.hpp"
+#include "mn_dispatch.hpp"
 
 #define BF_KMAX 128
 
@@ -92,17 +93,6 @@ __global__ void __launch_bounds__(256) k_bruteforce(MnDevIndex ix, const float *
     }
 }
 
-static int pick_nch_bf(int ld) {
-    int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 size_t mn_bruteforce_lds_bytes(int ld) { return (size_t)ld * sizeof(float) + 4 * BF_KMAX * (sizeof(float) + sizeof(int)); }
 
 void mn_launch_bruteforce(const MnDevIndex &ix, const float *d_queries, long long nq, int k, long long *d_out_ids,
@@ -111,21 +101,9 @@ void mn_launch_bruteforce(const MnDevIndex &ix, const float *d_queries, long lon
         return;
     size_t lds = mn_bruteforce_lds_bytes(ix.ld);
     dim3 grid((unsigned)nq), block(256);
-#define MN_BF(O, N) hipLaunchKernelGGL((k_bruteforce<O, N>), grid, block, lds, st, ix, d_queries, nq, k, d_out_ids)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_BF(MN_ORDER_SSE_V, 0);
-        return;
-    }
-    switch (pick_nch_bf(ix.ld)) {
-    case 1: MN_BF(MN_ORDER_WAVE_V, 1); break;
-    case 2: MN_BF(MN_ORDER_WAVE_V, 2); break;
-    case 3: MN_BF(MN_ORDER_WAVE_V, 3); break;
-    case 4: MN_BF(MN_ORDER_WAVE_V, 4); break;
-    case 6: MN_BF(MN_ORDER_WAVE_V, 6); break;
-    case 8: MN_BF(MN_ORDER_WAVE_V, 8); break;
-    default: MN_BF(MN_ORDER_WAVE_V, 0); break;
-    }
-#undef MN_BF
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        hipLaunchKernelGGL((k_bruteforce<O(), N()>), grid, block, lds, st, ix, d_queries, nq, k, d_out_ids);
+    });
 }
 
 

@@ -16,6 +16,7 @@
 // sources are sorted by batch index.
 #include "mn_dist.hpp"
 #include "mn_prune.hpp"
+#include "mn_dispatch.hpp"
 
 DEVI int *row_ptr(const MnDevIndex &ix, int node, int level) {
     if (level == 0)
@@ -379,17 +380,6 @@ __global__ void k_link_reset_counts(MnLinkArgs a) {
         a.count[a.touched[i]] = 0;
 }
 
-static int pick_nch_b(int ld) {
-    int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 static int reverse_lw(int WX) {
     const int LW = (WX + 64 + 63) & ~63; // the row is staged 64 links at a time, then one more / a chunk of 64 sources is appended
     return LW < 192 ? 192 : LW;
@@ -408,19 +398,7 @@ static void launch_reverse(const MnDevIndex &ix, const MnLinkArgs &a, int max_tu
 }
 
 static void launch_reverse_any(const MnDevIndex &ix, const MnLinkArgs &a, int max_tuples, hipStream_t st) {
-    if (ix.order == MN_ORDER_SSE_V) {
-        launch_reverse<MN_ORDER_SSE_V, 0>(ix, a, max_tuples, st);
-        return;
-    }
-    switch (pick_nch_b(ix.ld)) {
-    case 1: launch_reverse<MN_ORDER_WAVE_V, 1>(ix, a, max_tuples, st); break;
-    case 2: launch_reverse<MN_ORDER_WAVE_V, 2>(ix, a, max_tuples, st); break;
-    case 3: launch_reverse<MN_ORDER_WAVE_V, 3>(ix, a, max_tuples, st); break;
-    case 4: launch_reverse<MN_ORDER_WAVE_V, 4>(ix, a, max_tuples, st); break;
-    case 6: launch_reverse<MN_ORDER_WAVE_V, 6>(ix, a, max_tuples, st); break;
-    case 8: launch_reverse<MN_ORDER_WAVE_V, 8>(ix, a, max_tuples, st); break;
-    default: launch_reverse<MN_ORDER_WAVE_V, 0>(ix, a, max_tuples, st); break;
-    }
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) { launch_reverse<O(), N()>(ix, a, max_tuples, st); });
 }
 
 void mn_launch_link(const MnDevIndex &ix, const MnLinkArgs &a, int max_tuples, hipStream_t st) {

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define MN_WAVE 64
 
@@ -124,6 +125,15 @@ struct MnSearchArgs {
 // dynamic LDS a workgroup of this process may ask for: 64 KB, or what the device grants on request (mn_kernels.hip)
 size_t mn_lds_optin_limit();
 bool mn_lds_grant(const void *kernel, size_t bytes); // asks once per kernel and size; false = stay within 64 KB
+template <typename K> inline bool mn_lds_grant_for(K kernel, size_t bytes) { return mn_lds_grant(reinterpret_cast<const void *>(kernel), bytes); }
+// The latency kernels (k_beam_coop, k_insert_seq) request the rows of ALL listed neighbours next to the visited probe only when the
+// vectors do not fit the 256 MB Infinity Cache (a row is then an HBM round trip worth hiding: 1M x 768, one query 1.575 -> 1.52 ms);
+// on a cache-resident index the extra rows cost more than the probe (10k x 768: 0.58 -> 0.61 ms).  MN_SPEC_ROWS=0 / 1 forces.
+inline int mn_no_spec_rows(long long n_slots, int ld) {
+    const char *sr = getenv("MN_SPEC_ROWS");
+    const bool big = (size_t)n_slots * ld * sizeof(float) > ((size_t)256 << 20);
+    return sr ? (atoi(sr) == 0 ? 1 : 0) : (big ? 0 : 1);
+}
 
 // LDS budget per wavefront (items are 8 B: f32 distance bits, int32 slot)
 #ifndef MN_CAND_LDS
@@ -163,24 +173,24 @@ int mn_launch_bruteforce_mfma(const MnDevIndex &ix, const float *d_queries, long
 // exact search (mn_exact.hip).  Candidate pass on the matrix cores + re-score + certificate: kp = k + slack <= 64 list entries per
 // query, scratch = one allocation of mn_exact_mfma_scratch_bytes(), d_ctr [3] zeroed ([0] marked queries [1] rows re-scored [2] bound
 // violations), d_marked [nq].  Returns 1 when the device does not grant the LDS the lists need (nothing launched), else 0 / -1.
-size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp);
+// The self-join flavour (mn_hnsw_knn_graph), self not null: the queries are the slots s0 .. s0 + nq - 1 of the row
+// store itself (d_queries and d_allow are not looked at), a query never lists its own slot, only rows with d <= r are kept
+// (r = +inf: no cut) and a deleted query slot answers count -1.  Outputs, d_marked and d_qsel are the batch's own, indexed within it.
+struct MnExactSelf {
+    int s0;
+    float r;
+    void *d_xc; // [n_slots] the rows' constants: mn_launch_knn_prep_rows, once per call (the candidate pass alone reads them)
+};
+size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp, bool self = false);
 int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, int kp, const unsigned *d_allow,
                          void *scratch, long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr,
-                         int *d_marked, hipStream_t st);
+                         int *d_marked, const MnExactSelf *self, hipStream_t st);
 // the index's inner loop over every row for queries d_qsel[0..n) (null: 0..n-1), k <= 128; same LDS as k_bruteforce
 size_t mn_exact_valu_lds_bytes(int ld);
 int mn_launch_exact_valu(const MnDevIndex &ix, const float *d_queries, const int *d_qsel, long long n, int k, const unsigned *d_allow,
-                         long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
+                         long long *d_out_ids, float *d_out_d, int *d_out_cnt, const MnExactSelf *self, hipStream_t st);
 void mn_launch_exact_fill(long long nq, int k, long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st);
-// The self-join flavour (mn_hnsw_knn_graph): the queries are the slots s0 .. s0 + nq - 1 of the row store itself, a
-// query never lists its own slot, only rows with d <= r are kept (r = +inf: no cut) and a deleted query slot answers count -1.
-// Outputs are the batch's own: [nq][k], [nq][k], [nq].  d_xc [n_slots]: mn_launch_knn_prep_rows, once per call.  scratch:
-// mn_exact_mfma_scratch_bytes(ix, nq, kp) bytes are enough.  d_ctr and d_marked (indices within the batch) as above.
 void mn_launch_knn_prep_rows(const MnDevIndex &ix, void *d_xc, hipStream_t st);
-int mn_launch_knn_mfma(const MnDevIndex &ix, int s0, long long nq, int k, int kp, float r, const void *d_xc, void *scratch,
-                       long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr, int *d_marked, hipStream_t st);
-int mn_launch_knn_valu(const MnDevIndex &ix, int s0, const int *d_qsel, long long n, int k, float r, long long *d_out_ids,
-                       float *d_out_d, int *d_out_cnt, hipStream_t st);
 
 // sharded index (config 3): per-shard top-k lists gathered as [world][nq][k] → global top-k per query in the total order
 // (distance, shard rank, position)  (mn_kernels.hip)

@@ -16,7 +16,7 @@
 // are a range of slots of the row store itself (no padded copy), a query never admits its own slot, every list's threshold starts
 // at the radius and the answer is cut at d <= r.  SELF is a template parameter: the search flavour compiles without any of it.
 #include "mn_dist.hpp"
-#include <type_traits>
+#include "mn_dispatch.hpp"
 
 #define EX_KMAX 128 // k_exact_valu
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -542,17 +542,6 @@ __global__ void k_exact_fill(long long nq, int k, long long *out_ids, float *out
 }
 
 // ───────────────────────── host side ─────────────────────────
-static int ex_pick_nch(int ld) { // the instantiations k_bruteforce walks rows with
-    const int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 void mn_launch_exact_fill(long long nq, int k, long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st) {
     const long long n = nq * k > nq ? nq * k : nq;
     hipLaunchKernelGGL(k_exact_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, nq, k, d_out_ids, d_out_d, d_out_cnt);
@@ -560,34 +549,38 @@ void mn_launch_exact_fill(long long nq, int k, long long *d_out_ids, float *d_ou
 
 size_t mn_exact_valu_lds_bytes(int ld) { return (size_t)ld * sizeof(float) + 4 * EX_KMAX * (sizeof(float) + sizeof(int)); }
 
+// the index's inner loop over every row for queries d_qsel[0..n) (null: 0..n-1); the self-join's queries are the rows from slot s0
 int mn_launch_exact_valu(const MnDevIndex &ix, const float *d_queries, const int *d_qsel, long long n, int k, const unsigned *d_allow,
-                         long long *d_out_ids, float *d_out_d, int *d_out_cnt, hipStream_t st) {
+                         long long *d_out_ids, float *d_out_d, int *d_out_cnt, const MnExactSelf *self, hipStream_t st) {
     if (n <= 0)
         return 0;
-    if (k <= 0 || k > EX_KMAX)
+    if (k <= 0 || k > EX_KMAX || (self && (self->s0 < 0 || self->s0 >= ix.n_slots || self->r != self->r)))
         return -1;
     const size_t lds = mn_exact_valu_lds_bytes(ix.ld);
     const dim3 grid((unsigned)n), block(256);
-#define MN_EV(O, N)                                                                                                                 \
-    hipLaunchKernelGGL((k_exact_valu<O, N>), grid, block, lds, st, ix, d_queries, d_qsel, k, d_allow, d_out_ids, d_out_d, d_out_cnt,   \
-                       ExNoSelf())
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_EV(MN_ORDER_SSE_V, 0);
-    } else {
-        switch (ex_pick_nch(ix.ld)) {
-        case 1: MN_EV(MN_ORDER_WAVE_V, 1); break;
-        case 2: MN_EV(MN_ORDER_WAVE_V, 2); break;
-        case 3: MN_EV(MN_ORDER_WAVE_V, 3); break;
-        case 4: MN_EV(MN_ORDER_WAVE_V, 4); break;
-        case 6: MN_EV(MN_ORDER_WAVE_V, 6); break;
-        case 8: MN_EV(MN_ORDER_WAVE_V, 8); break;
-        default: MN_EV(MN_ORDER_WAVE_V, 0); break;
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        if (self) {
+            ExSelf sf;
+            sf.s0 = self->s0;
+            sf.r = self->r;
+            hipLaunchKernelGGL((k_exact_valu<O(), N(), ExSelf>), grid, block, lds, st, ix, ix.vectors + (size_t)self->s0 * ix.ld, d_qsel,
+                               k, (const unsigned *)nullptr, d_out_ids, d_out_d, d_out_cnt, sf);
+        } else {
+            hipLaunchKernelGGL((k_exact_valu<O(), N()>), grid, block, lds, st, ix, d_queries, d_qsel, k, d_allow, d_out_ids, d_out_d,
+                               d_out_cnt, ExNoSelf());
         }
-    }
-#undef MN_EV
+    });
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// One candidate pass's scratch, as byte offsets: the padded queries and their constants (zeroed together), the rows' constants, the
+// row chunks' partial lists.  The self-join reads its queries from the row store and brings the rows' constants along
+// (mn_launch_knn_prep_rows): its qpad and xc parts are empty.
+struct ExLayout {
+    int n_chunks, rows_per_chunk;
+    long long q_tiles;
+    size_t qpad, qc, xc, pd, pi, pc, total;
+};
 // row chunks as mn_brute_mfma_scratch_bytes cuts them
 static void ex_chunks(const MnDevIndex &ix, long long nq, int *n_chunks, int *rows_per_chunk) {
     const long long qt = (nq + EX_Q - 1) / EX_Q;
@@ -602,16 +595,23 @@ static void ex_chunks(const MnDevIndex &ix, long long nq, int *n_chunks, int *ro
     *n_chunks = (ix.n_slots + rpc - 1) / rpc;
     *rows_per_chunk = rpc;
 }
-
-static size_t ex_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp) {
-    int nc = 0, rpc = 0;
-    ex_chunks(ix, nq, &nc, &rpc);
-    const size_t nq_pad = (size_t)((nq + EX_Q - 1) / EX_Q) * EX_Q;
-    return ex_up(nq_pad * ix.ld * 4) + ex_up(nq_pad * 8) + ex_up((size_t)ix.n_slots * 8) + 2 * ex_up((size_t)nc * nq * kp * 4) +
-           ex_up((size_t)nc * nq * 4);
+static ExLayout ex_layout(const MnDevIndex &ix, long long nq, int kp, bool self) {
+    ExLayout L;
+    L.q_tiles = (nq + EX_Q - 1) / EX_Q;
+    ex_chunks(ix, nq, &L.n_chunks, &L.rows_per_chunk);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nq_pad = (size_t)L.q_tiles * EX_Q, list = up((size_t)L.n_chunks * nq * kp * 4);
+    L.qpad = 0;
+    L.qc = L.qpad + (self ? 0 : up(nq_pad * ix.ld * 4));
+    L.xc = L.qc + up(nq_pad * 8);
+    L.pd = L.xc + (self ? 0 : up((size_t)ix.n_slots * 8));
+    L.pi = L.pd + list;
+    L.pc = L.pi + list;
+    L.total = L.pc + up((size_t)L.n_chunks * nq * 4);
+    return L;
 }
+
+size_t mn_exact_mfma_scratch_bytes(const MnDevIndex &ix, long long nq, int kp, bool self) { return ex_layout(ix, nq, kp, self).total; }
 
 static void ex_bound_consts(int ld, float *uc, float *fl2) {
     // what gradual underflow can lose of either dot product (2^-150 per operation), with room to spare
@@ -623,47 +623,50 @@ static void ex_bound_consts(int ld, float *uc, float *fl2) {
     *fl2 = f;
 }
 
-template <typename K> static bool ex_grant(K kern, size_t bytes) { return mn_lds_grant(reinterpret_cast<const void *>(kern), bytes); }
-
-// Candidate pass + re-score + certificate for all nq queries.  d_ctr [3] must be zero on entry; d_marked [nq].  1: the device does
-// not grant the LDS the lists need (nothing was launched: the caller takes k_exact_valu); 0 / -1.
-int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, int kp, const unsigned *d_allow,
-                         void *scratch, long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr,
-                         int *d_marked, hipStream_t st) {
-    if (nq <= 0 || k <= 0 || kp < k || kp > 64 || ix.n_slots <= 0)
-        return -1;
+template <bool SELF>
+static int launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, int kp, const unsigned *d_allow,
+                             void *scratch, long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr,
+                             int *d_marked, const MnExactSelf *self, hipStream_t st) {
     const size_t lds = ex_mfma_lds_bytes(kp);
-    const bool granted = ix.metric == 1 ? ex_grant(k_exact_mfma<1>, lds) : ix.metric == 0 ? ex_grant(k_exact_mfma<0>, lds) : ex_grant(k_exact_mfma<2>, lds);
+    const bool granted = ix.metric == 1   ? mn_lds_grant_for(k_exact_mfma<1, SELF>, lds)
+                         : ix.metric == 0 ? mn_lds_grant_for(k_exact_mfma<0, SELF>, lds)
+                                          : mn_lds_grant_for(k_exact_mfma<2, SELF>, lds);
     if (!granted)
         return 1;
-    MnExactArgs a;
-    ex_chunks(ix, nq, &a.n_chunks, &a.rows_per_chunk);
-    const long long qt = (nq + EX_Q - 1) / EX_Q;
-    const size_t nq_pad = (size_t)qt * EX_Q;
+    typename ExArgs<SELF>::type a;
+    const ExLayout L = ex_layout(ix, nq, kp, SELF);
+    a.n_chunks = L.n_chunks;
+    a.rows_per_chunk = L.rows_per_chunk;
     unsigned char *p = static_cast<unsigned char *>(scratch);
-    float *qpad = reinterpret_cast<float *>(p);
-    p += ex_up(nq_pad * ix.ld * 4);
-    float2 *qc = reinterpret_cast<float2 *>(p);
-    p += ex_up(nq_pad * 8);
-    float2 *xc = reinterpret_cast<float2 *>(p);
-    p += ex_up((size_t)ix.n_slots * 8);
-    a.pd = reinterpret_cast<float *>(p);
-    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
-    a.pi = reinterpret_cast<int *>(p);
-    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
-    a.pc = reinterpret_cast<int *>(p);
-    // the padding queries of the last tile: zero rows, zero constants (their columns of the tile are never looked at)
-    if (hipMemsetAsync(qpad, 0, ex_up(nq_pad * ix.ld * 4) + ex_up(nq_pad * 8), st) != hipSuccess)
+    float *qpad = SELF ? nullptr : reinterpret_cast<float *>(p + L.qpad);
+    float2 *qc = reinterpret_cast<float2 *>(p + L.qc);
+    a.pd = reinterpret_cast<float *>(p + L.pd);
+    a.pi = reinterpret_cast<int *>(p + L.pi);
+    a.pc = reinterpret_cast<int *>(p + L.pc);
+    // the padding queries of the last tile: zero rows, zero constants (their columns of the tile are never looked at; the
+    // self-join's are neither read nor looked at)
+    if (hipMemsetAsync(p + L.qpad, 0, L.xc - L.qpad, st) != hipSuccess)
         return -1;
+    const float *rows = d_queries;
+    if constexpr (SELF)
+        rows = ix.vectors + (size_t)self->s0 * ix.ld;
     const size_t qlds = (size_t)ix.ld * 4;
     if (ix.order == MN_ORDER_SSE_V)
-        hipLaunchKernelGGL(k_exact_prep_q<MN_ORDER_SSE_V>, dim3((unsigned)nq), dim3(64), qlds, st, ix, d_queries, nq, qpad, qc);
+        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_SSE_V, SELF>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, qpad, qc);
     else
-        hipLaunchKernelGGL(k_exact_prep_q<MN_ORDER_WAVE_V>, dim3((unsigned)nq), dim3(64), qlds, st, ix, d_queries, nq, qpad, qc);
-    hipLaunchKernelGGL(k_exact_prep_rows, dim3((unsigned)(((long long)ix.n_slots * 16 + 255) / 256)), dim3(256), 0, st, ix, xc);
-    a.q = qpad;
+        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_WAVE_V, SELF>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, qpad, qc);
+    if constexpr (SELF) {
+        a.q = rows;
+        a.xc = static_cast<const float2 *>(self->d_xc);
+        a.s0 = self->s0;
+        a.r = self->r;
+        a.thr0 = nextafterf(self->r, __builtin_inff()); // lb < thr0 is lb <= r (r = +inf stays +inf)
+    } else {
+        mn_launch_knn_prep_rows(ix, p + L.xc, st);
+        a.q = qpad;
+        a.xc = reinterpret_cast<const float2 *>(p + L.xc);
+    }
     a.qc = qc;
-    a.xc = xc;
     a.allow = d_allow;
     a.nq = nq;
     a.k = k;
@@ -674,147 +677,41 @@ int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long
     a.out_cnt = d_out_cnt;
     a.ctr = d_ctr;
     a.marked = d_marked;
-    const dim3 grid((unsigned)qt, (unsigned)a.n_chunks);
+    const dim3 grid((unsigned)L.q_tiles, (unsigned)a.n_chunks);
     if (ix.metric == 1)
-        hipLaunchKernelGGL(k_exact_mfma<1>, grid, dim3(256), lds, st, ix, a);
+        hipLaunchKernelGGL((k_exact_mfma<1, SELF>), grid, dim3(256), lds, st, ix, a);
     else if (ix.metric == 0)
-        hipLaunchKernelGGL(k_exact_mfma<0>, grid, dim3(256), lds, st, ix, a);
+        hipLaunchKernelGGL((k_exact_mfma<0, SELF>), grid, dim3(256), lds, st, ix, a);
     else
-        hipLaunchKernelGGL(k_exact_mfma<2>, grid, dim3(256), lds, st, ix, a);
+        hipLaunchKernelGGL((k_exact_mfma<2, SELF>), grid, dim3(256), lds, st, ix, a);
     // re-score: 4 queries per workgroup while their padded copies fit 32 KB of LDS, else one
     const int wpb = (size_t)ix.ld * 16 <= 32 * 1024 ? 4 : 1;
     const dim3 rgrid((unsigned)((nq + wpb - 1) / wpb)), rblock(64 * wpb);
     const size_t rlds = (size_t)ix.ld * 4 * wpb;
-#define MN_ER(O, N) hipLaunchKernelGGL((k_exact_rescore<O, N>), rgrid, rblock, rlds, st, ix, a)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_ER(MN_ORDER_SSE_V, 0);
-    } else {
-        switch (ex_pick_nch(ix.ld)) {
-        case 1: MN_ER(MN_ORDER_WAVE_V, 1); break;
-        case 2: MN_ER(MN_ORDER_WAVE_V, 2); break;
-        case 3: MN_ER(MN_ORDER_WAVE_V, 3); break;
-        case 4: MN_ER(MN_ORDER_WAVE_V, 4); break;
-        case 6: MN_ER(MN_ORDER_WAVE_V, 6); break;
-        case 8: MN_ER(MN_ORDER_WAVE_V, 8); break;
-        default: MN_ER(MN_ORDER_WAVE_V, 0); break;
-        }
-    }
-#undef MN_ER
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        hipLaunchKernelGGL((k_exact_rescore<O(), N(), SELF>), rgrid, rblock, rlds, st, ix, a);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ───────────────────────── the self-join (mn_hnsw_knn_graph) ─────────────────────────
+// the rows' constants of the bound: the search computes them per call into its scratch, the self-join once for all its batches
 void mn_launch_knn_prep_rows(const MnDevIndex &ix, void *d_xc, hipStream_t st) {
     hipLaunchKernelGGL(k_exact_prep_rows, dim3((unsigned)(((long long)ix.n_slots * 16 + 255) / 256)), dim3(256), 0, st, ix,
                        static_cast<float2 *>(d_xc));
 }
 
-// One batch of query slots [s0, s0 + nq) through candidate pass, re-score and certificate.  The batch's scratch holds the query
-// constants [nq_pad] and the partial lists, cut as mn_launch_exact_mfma cuts them: mn_exact_mfma_scratch_bytes(ix, nq, kp) covers it.
-int mn_launch_knn_mfma(const MnDevIndex &ix, int s0, long long nq, int k, int kp, float r, const void *d_xc, void *scratch,
-                       long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr, int *d_marked, hipStream_t st) {
-    if (nq <= 0 || k <= 0 || kp < k || kp > 64 || s0 < 0 || s0 + nq > ix.n_slots || r != r)
+// Candidate pass + re-score + certificate for all nq queries, or for the query slots [s0, s0 + nq) of the self-join.  d_ctr [3] must be
+// zero on entry; d_marked [nq].  1: the device does not grant the LDS the lists need (nothing was launched: the caller takes
+// k_exact_valu); 0 / -1.
+int mn_launch_exact_mfma(const MnDevIndex &ix, const float *d_queries, long long nq, int k, int kp, const unsigned *d_allow,
+                         void *scratch, long long *d_out_ids, float *d_out_d, int *d_out_cnt, unsigned long long *d_ctr,
+                         int *d_marked, const MnExactSelf *self, hipStream_t st) {
+    if (nq <= 0 || k <= 0 || kp < k || kp > 64 || ix.n_slots <= 0)
         return -1;
-    const size_t lds = ex_mfma_lds_bytes(kp);
-    const bool granted = ix.metric == 1   ? ex_grant(k_exact_mfma<1, true>, lds)
-                         : ix.metric == 0 ? ex_grant(k_exact_mfma<0, true>, lds)
-                                          : ex_grant(k_exact_mfma<2, true>, lds);
-    if (!granted)
-        return 1;
-    MnKnnArgs a;
-    ex_chunks(ix, nq, &a.n_chunks, &a.rows_per_chunk);
-    const long long qt = (nq + EX_Q - 1) / EX_Q;
-    const size_t nq_pad = (size_t)qt * EX_Q;
-    unsigned char *p = static_cast<unsigned char *>(scratch);
-    float2 *qc = reinterpret_cast<float2 *>(p);
-    p += ex_up(nq_pad * 8);
-    a.pd = reinterpret_cast<float *>(p);
-    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
-    a.pi = reinterpret_cast<int *>(p);
-    p += ex_up((size_t)a.n_chunks * nq * kp * 4);
-    a.pc = reinterpret_cast<int *>(p);
-    // the padding queries of the last tile: zero constants (their rows of the tile are neither read nor looked at)
-    if (hipMemsetAsync(qc, 0, ex_up(nq_pad * 8), st) != hipSuccess)
+    if (!self)
+        return launch_exact_mfma<false>(ix, d_queries, nq, k, kp, d_allow, scratch, d_out_ids, d_out_d, d_out_cnt, d_ctr, d_marked,
+                                        nullptr, st);
+    if (self->s0 < 0 || self->s0 + nq > ix.n_slots || self->r != self->r)
         return -1;
-    const float *rows = ix.vectors + (size_t)s0 * ix.ld;
-    const size_t qlds = (size_t)ix.ld * 4;
-    if (ix.order == MN_ORDER_SSE_V)
-        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_SSE_V, true>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, nullptr, qc);
-    else
-        hipLaunchKernelGGL((k_exact_prep_q<MN_ORDER_WAVE_V, true>), dim3((unsigned)nq), dim3(64), qlds, st, ix, rows, nq, nullptr, qc);
-    a.q = rows;
-    a.qc = qc;
-    a.xc = static_cast<const float2 *>(d_xc);
-    a.allow = nullptr;
-    a.nq = nq;
-    a.k = k;
-    a.kp = kp;
-    ex_bound_consts(ix.ld, &a.uc, &a.fl2);
-    a.out_ids = d_out_ids;
-    a.out_d = d_out_d;
-    a.out_cnt = d_out_cnt;
-    a.ctr = d_ctr;
-    a.marked = d_marked;
-    a.s0 = s0;
-    a.r = r;
-    a.thr0 = nextafterf(r, __builtin_inff()); // lb < thr0 is lb <= r (r = +inf stays +inf)
-    const dim3 grid((unsigned)qt, (unsigned)a.n_chunks);
-    if (ix.metric == 1)
-        hipLaunchKernelGGL((k_exact_mfma<1, true>), grid, dim3(256), lds, st, ix, a);
-    else if (ix.metric == 0)
-        hipLaunchKernelGGL((k_exact_mfma<0, true>), grid, dim3(256), lds, st, ix, a);
-    else
-        hipLaunchKernelGGL((k_exact_mfma<2, true>), grid, dim3(256), lds, st, ix, a);
-    const int wpb = (size_t)ix.ld * 16 <= 32 * 1024 ? 4 : 1;
-    const dim3 rgrid((unsigned)((nq + wpb - 1) / wpb)), rblock(64 * wpb);
-    const size_t rlds = (size_t)ix.ld * 4 * wpb;
-#define MN_ER(O, N) hipLaunchKernelGGL((k_exact_rescore<O, N, true>), rgrid, rblock, rlds, st, ix, a)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_ER(MN_ORDER_SSE_V, 0);
-    } else {
-        switch (ex_pick_nch(ix.ld)) {
-        case 1: MN_ER(MN_ORDER_WAVE_V, 1); break;
-        case 2: MN_ER(MN_ORDER_WAVE_V, 2); break;
-        case 3: MN_ER(MN_ORDER_WAVE_V, 3); break;
-        case 4: MN_ER(MN_ORDER_WAVE_V, 4); break;
-        case 6: MN_ER(MN_ORDER_WAVE_V, 6); break;
-        case 8: MN_ER(MN_ORDER_WAVE_V, 8); break;
-        default: MN_ER(MN_ORDER_WAVE_V, 0); break;
-        }
-    }
-#undef MN_ER
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// the index's inner loop over every row for the batch's queries d_qsel[0..n) (null: 0..n-1), indices within the batch
-int mn_launch_knn_valu(const MnDevIndex &ix, int s0, const int *d_qsel, long long n, int k, float r, long long *d_out_ids,
-                       float *d_out_d, int *d_out_cnt, hipStream_t st) {
-    if (n <= 0)
-        return 0;
-    if (k <= 0 || k > EX_KMAX || s0 < 0 || s0 >= ix.n_slots || r != r)
-        return -1;
-    const size_t lds = mn_exact_valu_lds_bytes(ix.ld);
-    const dim3 grid((unsigned)n), block(256);
-    const float *rows = ix.vectors + (size_t)s0 * ix.ld;
-    ExSelf sf;
-    sf.s0 = s0;
-    sf.r = r;
-#define MN_EV(O, N)                                                                                                                 \
-    hipLaunchKernelGGL((k_exact_valu<O, N, ExSelf>), grid, block, lds, st, ix, rows, d_qsel, k, (const unsigned *)nullptr, d_out_ids,  \
-                       d_out_d, d_out_cnt, sf)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_EV(MN_ORDER_SSE_V, 0);
-    } else {
-        switch (ex_pick_nch(ix.ld)) {
-        case 1: MN_EV(MN_ORDER_WAVE_V, 1); break;
-        case 2: MN_EV(MN_ORDER_WAVE_V, 2); break;
-        case 3: MN_EV(MN_ORDER_WAVE_V, 3); break;
-        case 4: MN_EV(MN_ORDER_WAVE_V, 4); break;
-        case 6: MN_EV(MN_ORDER_WAVE_V, 6); break;
-        case 8: MN_EV(MN_ORDER_WAVE_V, 8); break;
-        default: MN_EV(MN_ORDER_WAVE_V, 0); break;
-        }
-    }
-#undef MN_EV
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_exact_mfma<true>(ix, nullptr, nq, k, kp, nullptr, scratch, d_out_ids, d_out_d, d_out_cnt, d_ctr, d_marked, self, st);
 }

@@ -24,6 +24,7 @@
 #include <unordered_map>
 
 #include "mn_dist.hpp"
+#include "mn_dispatch.hpp"
 
 // ───────────────────────── k_prep_rows ─────────────────────────
 // Everything derived from a row when it is written (upload_vectors): |v|² in the index's order (cosine) and the coded shadow
@@ -179,17 +180,6 @@ __global__ void __launch_bounds__(64)
         out[base + lane] = d;
 }
 
-static int pick_nch(int ld) {
-    int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 // the query and one staged row: past 64 KB (ld > 8192) the kernel asks for the opt-in; beyond what the device grants, -1 and
 // nothing launched
 size_t mn_dist_batch_lds_bytes(int ld) { return (size_t)ld * sizeof(float) * 2; }
@@ -198,7 +188,7 @@ template <int ORDER, int NCH>
 static int launch_dist_batch(int metric, const float *d_query, const float *d_rows, long long n, int dim, int ld, float *d_out,
                              hipStream_t st) {
     const size_t lds = mn_dist_batch_lds_bytes(ld);
-    if (lds > mn_lds_optin_limit() || !mn_lds_grant(reinterpret_cast<const void *>(k_dist_batch<ORDER, NCH>), lds))
+    if (lds > mn_lds_optin_limit() || !mn_lds_grant_for(k_dist_batch<ORDER, NCH>, lds))
         return -1;
     hipLaunchKernelGGL((k_dist_batch<ORDER, NCH>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, metric, d_query, d_rows, n,
                        dim, ld, d_out);
@@ -209,17 +199,9 @@ int mn_launch_dist_batch(int metric, int order, const float *d_query, const floa
                          float *d_out, hipStream_t st) {
     if (n <= 0)
         return 0;
-    if (order == MN_ORDER_SSE_V)
-        return launch_dist_batch<MN_ORDER_SSE_V, 0>(metric, d_query, d_rows, n, dim, ld, d_out, st);
-#define MN_DB(N) \
-    case N:      \
-        return launch_dist_batch<MN_ORDER_WAVE_V, N>(metric, d_query, d_rows, n, dim, ld, d_out, st);
-    switch (pick_nch(ld)) {
-        MN_DB(1) MN_DB(2) MN_DB(3) MN_DB(4) MN_DB(6) MN_DB(8)
-    default:
-        return launch_dist_batch<MN_ORDER_WAVE_V, 0>(metric, d_query, d_rows, n, dim, ld, d_out, st);
-    }
-#undef MN_DB
+    return mn_for_row_walk(order, ld, [&](auto O, auto N) {
+        return launch_dist_batch<O(), N()>(metric, d_query, d_rows, n, dim, ld, d_out, st);
+    });
 }
 
 #include "mn_beam.hpp"
@@ -485,7 +467,6 @@ bool mn_lds_grant(const void *kern, size_t bytes) {
     }
     return ok;
 }
-template <typename K> static bool lds_grant(K kern, size_t bytes) { return mn_lds_grant(reinterpret_cast<const void *>(kern), bytes); }
 
 template <int ORDER, int NCH, bool BUILD, bool WIDE>
 static void launch_coop(const MnDevIndex &ix, MnSearchArgs a, size_t base, size_t tot, hipStream_t st) {
@@ -495,7 +476,7 @@ static void launch_coop(const MnDevIndex &ix, MnSearchArgs a, size_t base, size_
         const size_t off = (tot + 15) & ~(size_t)15;
         for (int rows = 4; rows >= 2; rows >>= 1) {
             const size_t need = off + (size_t)MN_COOP_WAVES * mn_lat_tile_floats(ix.ld, rows) * sizeof(float);
-            if (need <= mn_lds_optin_limit() && lds_grant(k_beam_coop<ORDER, NCH, BUILD, WIDE>, need)) {
+            if (need <= mn_lds_optin_limit() && mn_lds_grant_for(k_beam_coop<ORDER, NCH, BUILD, WIDE>, need)) {
                 a.lat_tile_rows = rows;
                 a.lat_tile_off = (unsigned)off;
                 tot = need;
@@ -569,15 +550,7 @@ int mn_launch_search(const MnDevIndex &ix, const MnSearchArgs &a, bool build, hi
             launch_beam<MN_ORDER_SSE_V, 0>(ix, a, build, st);
         return 0;
     }
-    switch (pick_nch(ix.ld)) {
-    case 1: launch_beam<MN_ORDER_WAVE_V, 1>(ix, a, build, st); break;
-    case 2: launch_beam<MN_ORDER_WAVE_V, 2>(ix, a, build, st); break;
-    case 3: launch_beam<MN_ORDER_WAVE_V, 3>(ix, a, build, st); break;
-    case 4: launch_beam<MN_ORDER_WAVE_V, 4>(ix, a, build, st); break;
-    case 6: launch_beam<MN_ORDER_WAVE_V, 6>(ix, a, build, st); break;
-    case 8: launch_beam<MN_ORDER_WAVE_V, 8>(ix, a, build, st); break;
-    default: launch_beam<MN_ORDER_WAVE_V, 0>(ix, a, build, st); break;
-    }
+    mn_for_wave_walk(ix.ld, [&](auto O, auto N) { launch_beam<O(), N()>(ix, a, build, st); });
     return 0;
 }
 
@@ -625,21 +598,9 @@ void mn_launch_edge_rows(const MnDevIndex &ix, const int *d_row_slot, const int 
         return;
     size_t lds = mn_row_lds_bytes(ix.ld);
     dim3 grid(n_rows), block(64);
-#define MN_ER(O, N) hipLaunchKernelGGL((k_edge_rows<O, N>), grid, block, lds, st, ix, d_row_slot, d_row_level, n_rows, d_out_nbr, d_out_dist)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_ER(MN_ORDER_SSE_V, 0);
-        return;
-    }
-    switch (pick_nch(ix.ld)) {
-    case 1: MN_ER(MN_ORDER_WAVE_V, 1); break;
-    case 2: MN_ER(MN_ORDER_WAVE_V, 2); break;
-    case 3: MN_ER(MN_ORDER_WAVE_V, 3); break;
-    case 4: MN_ER(MN_ORDER_WAVE_V, 4); break;
-    case 6: MN_ER(MN_ORDER_WAVE_V, 6); break;
-    case 8: MN_ER(MN_ORDER_WAVE_V, 8); break;
-    default: MN_ER(MN_ORDER_WAVE_V, 0); break;
-    }
-#undef MN_ER
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        hipLaunchKernelGGL((k_edge_rows<O(), N()>), grid, block, lds, st, ix, d_row_slot, d_row_level, n_rows, d_out_nbr, d_out_dist);
+    });
 }
 
 // ───────────────────────── k_merge_topk ─────────────────────────

@@ -9,6 +9,7 @@
 // (≈1 ms per insert); the batch-synchronous schedule (mn_build.hip) is the throughput path.
 #include "mn_beam.hpp"
 #include "mn_prune.hpp"
+#include "mn_dispatch.hpp"
 
 struct MnSeqArgs {
     const int *slots; // nodes to insert, in order
@@ -379,17 +380,6 @@ static size_t seq_pre_bytes(const MnDevIndex &ix, int *rows, int *w) {
     return (size_t)*rows * *w * sizeof(float) + (size_t)((*rows + 3) & ~3) * sizeof(int);
 }
 
-static int pick_nch_s(int ld) {
-    int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 void mn_launch_insert_seq(const MnDevIndex &ix, const int *d_slots, int n, int ef, int *d_state, unsigned *bitmap0,
                           long long bm0_words, unsigned *bitmap_up, long long bmu_words, uint2 *cand_ovf, int cand_gcap,
                           uint2 *res_ovf, int res_gcap, unsigned long long *counters, hipStream_t st, int *chlog, int chcap) {
@@ -423,11 +413,7 @@ void mn_launch_insert_seq(const MnDevIndex &ix, const int *d_slots, int n, int e
     if (pe && atoi(pe) == 0)
         pre = 0;
     a.pre_rows = a.pre_w = a.wave_floats = a.lat_tile_rows = 0;
-    {
-        const char *sr = getenv("MN_SPEC_ROWS"); // (see prepare_search_ws, mn_index.hip: only for indexes beyond the Infinity Cache)
-        const bool big = (size_t)ix.n_slots * ix.ld * sizeof(float) > ((size_t)256 << 20);
-        a.no_spec_rows = sr ? (atoi(sr) == 0 ? 1 : 0) : (big ? 0 : 1);
-    }
+    a.no_spec_rows = mn_no_spec_rows(ix.n_slots, ix.ld);
     const size_t lds0 = lds;
     const char *te = getenv("MN_LAT_TILE"); // MN_LAT_TILE=0: no distance tiles
     for (int rows = ix.order == MN_ORDER_SSE_V && ix.ld >= 256 && !(te && atoi(te) == 0) ? 4 : 0; rows >= 0; rows = rows == 4 ? 2 : rows == 2 ? 0 : -1) {
@@ -448,45 +434,29 @@ void mn_launch_insert_seq(const MnDevIndex &ix, const int *d_slots, int n, int e
     }
     const char *co = getenv("MN_COOP"); // MN_COOP=0: the inserting wavefront alone
     const dim3 blk(co && atoi(co) == 0 ? 64 : MN_SEQ_WAVES * 64);
-#define MN_SQ(O, N)                                                                                                          \
-    do {                                                                                                                     \
-        if (lds > 64 * 1024) {                                                                                               \
-            const void *kp = ix.WX > 64 ? reinterpret_cast<const void *>(k_insert_seq<O, N, true>)                           \
-                                        : reinterpret_cast<const void *>(k_insert_seq<O, N, false>);                         \
-            if (!mn_lds_grant(kp, lds)) { /* not granted: without the tile (and, if that is still too much, without the rest) */ \
-                a.lat_tile_rows = 0;                                                                                         \
-                a.wave_floats = a.pre_rows ? ix.ld : 0;                                                                      \
-                lds = lds0 + pre + (size_t)MN_SEQ_WAVES * a.wave_floats * sizeof(float);                                     \
-                if (lds > 64 * 1024) {                                                                                       \
-                    a.pre_rows = a.pre_w = a.wave_floats = 0;                                                                \
-                    lds = lds0;                                                                                              \
-                }                                                                                                            \
-                if (lds > 64 * 1024)                                                                                         \
-                    (void)mn_lds_grant(kp, lds); /* the kernel's own arrays alone pass 64 KB: refused = the launch fails */  \
-            }                                                                                                                \
-        }                                                                                                                    \
-        if (getenv("MN_LAT_DEBUG"))                                                                                          \
-            fprintf(stderr, "[mn] k_insert_seq: distance tile of %d rows per wavefront, %zu bytes of LDS\n", a.lat_tile_rows,  \
-                    lds);                                                                                                    \
-        if (ix.WX > 64)                                                                                                      \
-            hipLaunchKernelGGL((k_insert_seq<O, N, true>), dim3(1), blk, lds, st, ix, a, base);                              \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((k_insert_seq<O, N>), dim3(1), blk, lds, st, ix, a, base);                                    \
-    } while (0)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_SQ(MN_ORDER_SSE_V, 0);
-        return;
-    }
-    switch (pick_nch_s(ix.ld)) {
-    case 1: MN_SQ(MN_ORDER_WAVE_V, 1); break;
-    case 2: MN_SQ(MN_ORDER_WAVE_V, 2); break;
-    case 3: MN_SQ(MN_ORDER_WAVE_V, 3); break;
-    case 4: MN_SQ(MN_ORDER_WAVE_V, 4); break;
-    case 6: MN_SQ(MN_ORDER_WAVE_V, 6); break;
-    case 8: MN_SQ(MN_ORDER_WAVE_V, 8); break;
-    default: MN_SQ(MN_ORDER_WAVE_V, 0); break;
-    }
-#undef MN_SQ
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        if (lds > 64 * 1024) {
+            const void *kp = ix.WX > 64 ? reinterpret_cast<const void *>(k_insert_seq<O(), N(), true>)
+                                        : reinterpret_cast<const void *>(k_insert_seq<O(), N(), false>);
+            if (!mn_lds_grant(kp, lds)) { // not granted: without the tile (and, if that is still too much, without the rest)
+                a.lat_tile_rows = 0;
+                a.wave_floats = a.pre_rows ? ix.ld : 0;
+                lds = lds0 + pre + (size_t)MN_SEQ_WAVES * a.wave_floats * sizeof(float);
+                if (lds > 64 * 1024) {
+                    a.pre_rows = a.pre_w = a.wave_floats = 0;
+                    lds = lds0;
+                }
+                if (lds > 64 * 1024)
+                    (void)mn_lds_grant(kp, lds); // the kernel's own arrays alone pass 64 KB: refused = the launch fails
+            }
+        }
+        if (getenv("MN_LAT_DEBUG"))
+            fprintf(stderr, "[mn] k_insert_seq: distance tile of %d rows per wavefront, %zu bytes of LDS\n", a.lat_tile_rows, lds);
+        if (ix.WX > 64)
+            hipLaunchKernelGGL((k_insert_seq<O(), N(), true>), dim3(1), blk, lds, st, ix, a, base);
+        else
+            hipLaunchKernelGGL((k_insert_seq<O(), N()>), dim3(1), blk, lds, st, ix, a, base);
+    });
 }
 
 #ifdef MN_PHASE_TIMING

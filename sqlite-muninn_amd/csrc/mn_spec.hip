@@ -18,6 +18,7 @@
 // (insert, layer) is then redone by one wavefront in list order.
 #include "mn_beam.hpp"
 #include "mn_prune.hpp"
+#include "mn_dispatch.hpp"
 
 #define MN_SPEC_MAX_WAVES 8
 
@@ -448,17 +449,6 @@ __global__ void __launch_bounds__(MN_SPEC_MAX_WAVES * 64) k_spec_commit(MnDevInd
     }
 }
 
-static int pick_nch_p(int ld) {
-    int need = (ld + 255) / 256;
-    if (need <= 1) return 1;
-    if (need <= 2) return 2;
-    if (need <= 3) return 3;
-    if (need <= 4) return 4;
-    if (need <= 6) return 6;
-    if (need <= 8) return 8;
-    return 0;
-}
-
 #define MN_SPEC_SHARED_BYTES ((16 + 64 + 64 + 64 + 64 * 64) * sizeof(int))
 static size_t spec_wave_bytes(int ld) { return (3 * 128 * sizeof(int) + (size_t)ld * sizeof(float) + 15) & ~(size_t)15; }
 // k_spec_commit with its one wavefront (it never asks for more than 64 KB)
@@ -494,26 +484,11 @@ void mn_launch_spec_commit(const MnDevIndex &ix, const int *d_slots, int W, int 
     nw = nw < 1 ? 1 : (nw > MN_SPEC_MAX_WAVES ? MN_SPEC_MAX_WAVES : nw);
     const size_t lds = MN_SPEC_SHARED_BYTES + (size_t)nw * a.wave_bytes;
     const size_t lds_pre = (size_t)nw * a.wave_bytes;
-#define MN_SP(O, N)                                                                                                              \
-    do {                                                                                                                         \
-        if (a.pre_act)                                                                                                           \
-            hipLaunchKernelGGL((k_spec_prepare<O, N>), dim3(W), dim3(nw * 64), lds_pre, st, ix, a);                              \
-        hipLaunchKernelGGL((k_spec_commit<O, N>), dim3(1), dim3(nw * 64), lds, st, ix, a);                                       \
-    } while (0)
-    if (ix.order == MN_ORDER_SSE_V) {
-        MN_SP(MN_ORDER_SSE_V, 0);
-        return;
-    }
-    switch (pick_nch_p(ix.ld)) {
-    case 1: MN_SP(MN_ORDER_WAVE_V, 1); break;
-    case 2: MN_SP(MN_ORDER_WAVE_V, 2); break;
-    case 3: MN_SP(MN_ORDER_WAVE_V, 3); break;
-    case 4: MN_SP(MN_ORDER_WAVE_V, 4); break;
-    case 6: MN_SP(MN_ORDER_WAVE_V, 6); break;
-    case 8: MN_SP(MN_ORDER_WAVE_V, 8); break;
-    default: MN_SP(MN_ORDER_WAVE_V, 0); break;
-    }
-#undef MN_SP
+    mn_for_row_walk(ix.order, ix.ld, [&](auto O, auto N) {
+        if (a.pre_act)
+            hipLaunchKernelGGL((k_spec_prepare<O(), N()>), dim3(W), dim3(nw * 64), lds_pre, st, ix, a);
+        hipLaunchKernelGGL((k_spec_commit<O(), N()>), dim3(1), dim3(nw * 64), lds, st, ix, a);
+    });
 }
 
 // HIP loads a translation unit's code object on the first use of one of its kernels (several milliseconds for these units): an

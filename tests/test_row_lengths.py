@@ -6,7 +6,9 @@ entry of DIMS reaches a stated combination; the tests check every kernel family 
 bit for bit (ids, distance bits, counts, graphs) — and the geometry each entry claims is asserted from MN_LAT_DEBUG, not assumed.
 Family (f) is the exact search (csrc/mn_exact.hip): k_exact_rescore<ORDER, NCH> and k_exact_valu<ORDER, NCH> at every NCH in both
 orders, the re-score's two launch shapes (4 queries per workgroup while 16·ld bytes fit 32 KB, one above: ld > 2048) and
-k_exact_mfma's partial last 32-float stage (ld % 32 != 0)."""
+k_exact_mfma's partial last 32-float stage (ld % 32 != 0).
+Family (g) is the self-join of the same kernels (mn_hnsw_knn_graph): k_exact_rescore<ORDER, NCH, true>, k_exact_valu<ORDER, NCH, ExSelf>
+and k_exact_prep_q<ORDER, true> at the row lengths of family (f), in query batches of 128 + 128 + 44 slots."""
 import os
 import subprocess
 import sys
@@ -14,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import test_knn_graph as kg
 from test_exact_search import check, distances, exact, reference
 from util import check_topk_f64, gauss, same_bits
 
@@ -53,6 +56,9 @@ BRUTE_MFMA_DIMS = [226, 345, 953, 1283, 2050]
 # family (f): NCH 1, 2, 3, 4, 6, 8, 8, 0, 0; ld 228, 348, 708, 1284 and 2052 are not whole 32-float stages of k_exact_mfma; 2048 is the
 # last row re-scored 4 queries per workgroup, 2050 the first re-scored one per workgroup
 EXACT_DIMS = [226, 345, 708, 1021, 1283, 1999, 2048, 2050, 4096]
+# family (g): the same row lengths; every row is a query, in batches of KNN_BATCH slots: two whole ones and a ragged last tile
+KNN_DIMS = EXACT_DIMS
+KNN_N, KNN_BATCH = 300, 128
 
 
 def _ld(dim):
@@ -88,6 +94,9 @@ def test_table_states_what_the_dispatch_picks_and_reaches_every_path():
     assert any(_ld(d) % 32 != 0 for d in EXACT_DIMS)
     assert {_ld(d) * 16 <= 32768 for d in EXACT_DIMS} == {True, False}
     assert _ld(2048) * 16 == 32768 and 2050 in EXACT_DIMS  # both sides of the re-score's switch, at the switch
+    assert {DIMS[d][0] for d in KNN_DIMS} == {0, 1, 2, 3, 4, 6, 8}
+    assert {_ld(d) * 16 <= 32768 for d in KNN_DIMS} == {True, False}
+    assert KNN_BATCH % 128 == 0 and KNN_N // KNN_BATCH == 2 and 0 < KNN_N % KNN_BATCH < 128  # 128 + 128 + 44 query slots
 
 
 def _orders(gpu, orc):
@@ -372,6 +381,41 @@ def test_exact_search(gpu, orc, monkeypatch, dim):
                     monkeypatch.delenv(name)
                 check(got, want, key)
                 assert st["n_mfma_queries"] == (nq if k <= 32 and not env else 0), (key, st)
+            g.close()
+
+
+# ───────────────────────── (g) the exact k-NN graph of the index's own rows ─────────────────────────
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", KNN_DIMS)
+def test_knn_graph(gpu, orc, monkeypatch, dim):
+    """the self-join's candidate pass + re-score (default), its walk forced (MN_EXACT=valu) and its walk by k (33 > 32), in three
+    query batches: test_knn_graph's reference (every live row's other live rows under (d, slot)), ids, distance bits and counts,
+    count -1 at the deleted slots, for every metric in both orders"""
+    X = gauss(KNN_N, dim, 130 + dim)
+    X[17] = X[3]  # exact duplicate rows: each is the other's neighbour, the lower slot first among ties
+    ids = np.arange(100, 100 + KNN_N, dtype=np.int64)
+    for metric in METRICS:
+        for tag, go, oo in _orders(gpu, orc):
+            assert go == oo  # (Case carries one order for the oracle's distances and the index)
+            c = kg.Case(orc, metric, oo, X, ids)
+            d1 = c.D[1].copy()
+            d1[1] = np.inf
+            top1 = int(np.argmin(d1))  # row 1's would-be nearest goes, and a slot of the ragged last batch
+            c.set_dead({top1, 40, 290} - {3, 17})
+            n_live = len(c.live)
+            assert n_live == KNN_N - len(c.dead) and len(c.dead) in (2, 3)
+            g = kg.make_index(gpu, c)
+            for k, path in ((10, {}), (10, {"MN_EXACT": "valu"}), (33, {})):
+                key = (metric, tag, k, path)
+                want = c.reference(k)
+                assert (want[2][c.dead] == -1).all() and (want[2][c.live] == k).all(), key
+                assert top1 in (3, 17) or ids[top1] not in want[0][1], key
+                with kg.env(monkeypatch, path, {"MN_KNN_BATCH": str(KNN_BATCH)}):
+                    got, st = kg.knn(g, k)
+                kg.check(got, want, key)
+                assert st["n_queries"] == n_live, (key, st)
+                assert st["n_mfma_queries"] == (n_live if k <= 32 and not path else 0), (key, st)
             g.close()
 
 
