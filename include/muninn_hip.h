@@ -282,6 +282,53 @@ int mn_hnsw_knn_graph(mn_index *idx, int k, float max_distance, int64_t *out_ids
 /* outputs in device memory on idx's device; returns once the kernels have finished */
 int mn_hnsw_knn_graph_dev(mn_index *idx, int k, float max_distance, int64_t *d_out_ids, float *d_out_dists, int *d_out_counts);
 
+/* ---- entity resolution: the middle stages of muninn_extract_er (src/llama_er.c, src/string_sim.c) ----
+ * Names are byte strings in one arena: name s is bytes[off[s] .. off[s + 1]), off monotone, no terminator; at most 4096 bytes per
+ * name (the reference allocates for any length: a documented deviation, refused before any launch).  Bytes, not code points,
+ * as in the reference.  Every argument is checked on the host before anything is launched; errors: -1 + mn_last_error(). */
+typedef struct {
+    int32_t r1, r2; /* entity indices, r1 < r2 */
+    double weight;
+} mn_er_edge; /* MatchEdge (src/llama_er.c:41-44) */
+typedef enum { MN_ER_GUARD_NONE = 0, MN_ER_GUARD_SAME_SOURCE = 1, MN_ER_GUARD_DIFF_TYPE = 2 } mn_er_guard; /* :130-136 */
+typedef enum {
+    MN_ER_GRAPH = 0, /* the reference's blocking: every entity's stored vector searched through the graph at k + 1, ef 2 (k + 1) */
+    MN_ER_EXACT = 1  /* mn_hnsw_knn_graph at k: the exact neighbours under the threshold */
+} mn_er_blocking;
+typedef struct {
+    int64_t n_candidates, n_edges;
+    int64_t n_jw_short, n_jw_long; /* pairs that ran the matching loop one per lane / one per wavefront */
+    double blocking_ms, candidates_ms, score_ms; /* device time per stage */
+} mn_er_stats;
+/* jaro_winkler(name a[p], name b[p]) (src/string_sim.c:11-96) for p < n_pairs, bit-identical f64.  Pairs of names of at most 64
+ * bytes go one per lane, longer ones one per wavefront, in the same launch.  0 / -1. */
+int mn_er_jaro_winkler(int64_t n_pairs, const unsigned char *bytes, const int64_t *off, int64_t n_str, const int *a, const int *b,
+                       int device, double *out);
+/* The candidate loop of src/llama_er.c:237-284 over a search's answer: ent_ids[n] are the entities' rowids (unique) in entity order;
+ * nbr_ids / nbr_dists [n][kk] and counts[n] each entity's neighbours (count <= 0: the entity has no vector).  An id twice in ent_ids is an
+ * argument error (found on the device, reported before any pair is written); an id twice in ONE list — no search answers so — is
+ * not checked and leaves the pairs of that id undefined.  An entry survives when its id is not the entity's own, !((double)d > dist_threshold), and the id is an entity.
+ * Output: the unordered pairs (r1 < r2, entity indices) in order of first appearance over (entity, list position), each with the
+ * smallest distance of its appearances — the reference's list without its linear scan.  r1, r2, dist are the caller's, n * kk
+ * entries each.  Returns the pair count, or -1. */
+int64_t mn_er_candidates(int n, int kk, const int64_t *ent_ids, const int64_t *nbr_ids, const float *nbr_dists, const int *counts,
+                         double dist_threshold, int device, int *r1, int *r2, double *dist);
+/* The type guard and scoring cascade of src/llama_er.c:295-332 per candidate, in order: source ids (0 = empty, never blocks; NULL =
+ * all empty) against `guard`; names equal -> 1.0; equal after lowering ASCII A-Z -> 0.9; else
+ * jw_weight * jaro_winkler(lowered names) + (1.0 - jw_weight) * (1.0 - dist); kept when score >= match_threshold.  edges (the
+ * caller's, n_cand entries) receives the kept candidates in candidate order.  Returns the edge count, or -1. */
+int64_t mn_er_score(int64_t n_cand, const int *r1, const int *r2, const double *dist, int n, const unsigned char *bytes,
+                    const int64_t *off, const int *source_id, int guard, double jw_weight, double match_threshold, int device,
+                    mn_er_edge *edges);
+/* Stages 2 and 3 of muninn_extract_er (src/llama_er.c:207-332) on the index's device and stream: blocking, candidates, scores.
+ * Only names go up and only edges come down.  An entity whose id is absent from the index or deleted has no vector and no list
+ * (:240-243).  1 <= k <= 127.  MN_ER_EXACT cuts at the largest float not above dist_threshold, so that the float cut and the
+ * reference's double comparison agree on every f32 distance.  edges: the caller's, n * (k + 1) entries.  stats may be NULL.
+ * Returns the edge count, or -1. */
+int64_t mn_hnsw_er_edges(mn_index *idx, int n, const int64_t *ent_ids, const unsigned char *bytes, const int64_t *off,
+                         const int *source_id, int k, double dist_threshold, double jw_weight, double match_threshold, int guard,
+                         int blocking, mn_er_edge *edges, mn_er_stats *stats);
+
 /* ---- graph_csr.h / graph_community.c replacements (a18-a22) ---- */
 typedef struct mn_graph mn_graph; /* device-resident adjacency: GraphData.out / .in (src/graph_load.h:27-37) as two
                                      CsrArray (src/graph_csr.h:27-34: int32 offsets[V+1], int32 targets[E], f64 weights[E]|NULL) */

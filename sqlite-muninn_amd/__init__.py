@@ -10,7 +10,7 @@ The directory name contains a hyphen (it is the project name); import it through
 from .build import LIB, build  # noqa: F401
 from .hnsw import (BUILD_BATCHED, BUILD_SEQUENTIAL, METRIC, ORDER_SSE, ORDER_WAVE, HnswIndex, MuninnHipError, ShardedIndex,  # noqa: F401
                    device_count, lib, max_dim, vec_dist_batch, vec_parse_metric)
-from . import graph  # noqa: E402,F401
+from . import er, graph  # noqa: E402,F401
 from .graph import LEIDEN_BATCHED, LEIDEN_SEQUENTIAL, N2V_BATCHED, N2V_SEQUENTIAL, Graph, node2vec_train  # noqa: E402,F401
 
 

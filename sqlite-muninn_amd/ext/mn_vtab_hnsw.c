@@ -1526,6 +1526,27 @@ int mn_vtab_hnsw_fill_from_n2v(sqlite3 *db, const char *table, int n, const int 
     return 1;
 }
 
+/* muninn_extract_er (mn_er_sql.c): the device index behind a live hnsw_index table of this connection, its queued rows applied
+ * first — what hnsw_knn_graph does before it asks.  NULL + *err (sqlite3_mprintf) when there is no such table or the rows fail. */
+mn_index *mn_vtab_hnsw_index_of(sqlite3 *db, const char *table, char **err) {
+    VtabHnsw *v = live_find(db, table);
+    if (!v) { /* not connected yet on this connection: touching the table connects it */
+        char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", table);
+        sqlite3_exec(db, sql, 0, 0, 0);
+        sqlite3_free(sql);
+        v = live_find(db, table);
+    }
+    if (!v) {
+        *err = sqlite3_mprintf("no hnsw_index table named '%s'", table);
+        return 0;
+    }
+    if (flush_pending(v) != SQLITE_OK) {
+        *err = sqlite3_mprintf("%s", v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
+        return 0;
+    }
+    return v->index;
+}
+
 int mn_register_hnsw_module(sqlite3 *db) {
     int rc = sqlite3_create_module(db, "hnsw_index", &hnsw_module, 0); /* src/hnsw_vtab.c:805-807 */
     if (rc == SQLITE_OK)

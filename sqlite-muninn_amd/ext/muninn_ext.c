@@ -6,7 +6,7 @@
  * the first failure aborts with *pzErrMsg set via sqlite3_mprintf.  Registered here: the
  * hot-path surface of SURVEY §8(b) — `hnsw_index` (+ `hnsw0` alias), `node2vec_train`,
  * `graph_leiden` — and §8 f-4's `graph_components` / `graph_pagerank` / `graph_node_betweenness` / `graph_edge_betweenness` /
- * `graph_degree` / `graph_closeness`, each backed by libmuninn_hip.so
+ * `graph_degree` / `graph_closeness`, and the reference's `muninn_extract_er` (src/llama_er.c), each backed by libmuninn_hip.so
  * (include/muninn_hip.h).
  */
 #include "mn_sqlite_abi.h"
@@ -18,6 +18,7 @@ int mn_register_graph_functions(sqlite3 *db) __attribute__((weak));
 int mn_register_graph_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_betweenness_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_centrality_tvfs(sqlite3 *db) __attribute__((weak));
+int mn_register_er_functions(sqlite3 *db) __attribute__((weak));
 
 #ifdef _WIN32
 __declspec(dllexport)
@@ -54,6 +55,13 @@ int sqlite3_muninn_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
         rc = mn_register_centrality_tvfs(db);
         if (rc != SQLITE_OK) {
             *pzErrMsg = sqlite3_mprintf("muninn: failed to register centrality TVFs");
+            return rc;
+        }
+    }
+    if (mn_register_er_functions) {
+        rc = mn_register_er_functions(db);
+        if (rc != SQLITE_OK) {
+            *pzErrMsg = sqlite3_mprintf("muninn: failed to register entity resolution functions");
             return rc;
         }
     }

@@ -47,6 +47,28 @@ class BuildStats(C.Structure):
                 ("batches", C.c_int64), ("nodes", C.c_int64)]
 
 
+class ErEdge(C.Structure):  # mn_er_edge
+    _fields_ = [("r1", C.c_int32), ("r2", C.c_int32), ("weight", C.c_double)]
+
+
+class ErStats(C.Structure):  # mn_er_stats
+    _fields_ = [("n_candidates", C.c_int64), ("n_edges", C.c_int64), ("n_jw_short", C.c_int64), ("n_jw_long", C.c_int64),
+                ("blocking_ms", C.c_double), ("candidates_ms", C.c_double), ("score_ms", C.c_double)]
+
+
+_u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
+_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+
+# the entity-resolution entry points (er.py is their Python face); part of SYMBOLS, bound with it
+ER_SYMBOLS = [
+    ("mn_er_jaro_winkler", C.c_int, [C.c_int64, _u8p, _i64p, C.c_int64, _i32p, _i32p, C.c_int, _f64p]),
+    ("mn_er_candidates", C.c_int64, [C.c_int, C.c_int, _i64p, _i64p, _f32p, _i32p, C.c_double, C.c_int, _i32p, _i32p, _f64p]),
+    ("mn_er_score", C.c_int64, [C.c_int64, _i32p, _i32p, _f64p, C.c_int, _u8p, _i64p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                C.c_int, C.c_void_p]),
+    ("mn_hnsw_er_edges", C.c_int64, [C.c_void_p, C.c_int, _i64p, _u8p, _i64p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                     C.c_int, C.c_int, C.c_void_p, C.POINTER(ErStats)]),
+]
+
 # every symbol include/muninn_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("mn_abi_version", C.c_int, []),
@@ -134,7 +156,7 @@ SYMBOLS = [
     ("mn_shards_search", C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_void_p]),
     ("mn_shards_search_batch", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_int, _i64p, _f32p, _i32p]),
     ("mn_shards_last_error", C.c_char_p, []),
-]
+] + ER_SYMBOLS
 
 _lib = None
 
