@@ -397,6 +397,31 @@ int mn_graph_closeness(mn_graph *g, int direction, int normalized, double *out);
  * normalized && n > 1.  Any output pointer may be NULL.  0 / -1. */
 int mn_graph_degree(mn_graph *g, int normalized, double *in_deg, double *out_deg, double *degree, double *centrality);
 
+typedef struct {
+    int64_t rows, levels, chunks, edges_scanned; /* levels: level passes run, each one host round trip, summed over the chunks */
+    double device_ms;
+} mn_bfs_stats;
+/* run_bfs (src/graph_tvf.c:230-309) for n_seeds start nodes at once: per seed the rows (node, depth, parent) in the order
+ * the reference's queue pops them — level by level, a level's nodes ordered by (parent's position in the previous level, index
+ * in the parent's list: out-list before in-list, :284-297), the parent being the first neighbour in that order to reach the
+ * node; a node at max_depth is not expanded (:282).  A level-synchronous pass over all seeds of a chunk (csrc/mn_bfs.hip): the
+ * order is a minimum over edge numbers, so it does not depend on arrival order, launch shape or chunking.  direction 0 = both,
+ * 1 = forward, 2 = reverse, with mn_graph_betweenness's meaning and the same requirement on which lists the graph holds (a
+ * graph whose lists were filled for another direction is refused).  Seeds may repeat, each gets its own answer; n_seeds == 0
+ * answers 0 rows; max_depth <= 0 answers the seed rows; weights are ignored.  row_off[n_seeds + 1]: seed i's rows are
+ * row_off[i] .. row_off[i + 1] - 1 of mn_graph_bfs_rows.  Seeds go through in chunks under a scratch budget: half of the free
+ * device memory, or MN_BFS_SCRATCH_MB MiB (fractions allowed) — 64 bytes per node per seed of a chunk (4 of them the visited
+ * word, filled once per allocation and reset after a chunk only where the chunk's rows name it; the rest bounds the rows and
+ * their sort), at least one seed, at most (2^31 - 1) / n; the scratch stays with the handle until mn_graph_destroy.  A seed
+ * outside 0 .. n - 1, n_seeds < 0, a missing list, n > 2^26 or more than 2^32 - 3 list entries is an error before any launch.
+ * stats may be NULL.  Sets mn_graph_last_ms (the kernels, without the host's waits between levels).  Returns the row count,
+ * or -1 with mn_graph_last_error set. */
+int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, const int *seeds, int max_depth, int64_t *row_off,
+                     mn_bfs_stats *stats);
+/* The rows of the last mn_graph_bfs on this handle (they stay with it until the next call or mn_graph_destroy): node, depth and
+ * parent (-1 for a seed) of each, row count as returned; any pointer may be NULL.  0 / -1. */
+int mn_graph_bfs_rows(mn_graph *g, int *node, int *depth, int *parent);
+
 /* ---- node2vec.c replacements (a14-a17) ---- */
 typedef struct {
     int dim;            /* 1..1024 (src/node2vec.c:447) */

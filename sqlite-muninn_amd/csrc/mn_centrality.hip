@@ -12,19 +12,6 @@
 
 // ───────────────────────── what the entry points share ─────────────────────────
 
-// Scratch a call may take: half of what the device has free once `reserve` bytes are set aside, at least 256 MiB — unless
-// the environment variable `env` gives a decimal number of MiB (fractions allowed, <= 0 means 0).
-static size_t scratch_budget(const char *env, size_t reserve) {
-    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        budget = std::max<size_t>((size_t)256 << 20, (free_b > reserve ? free_b - reserve : 0) / 2);
-    if (const char *e = getenv(env)) {
-        const double mb = strtod(e, nullptr);
-        budget = mb > 0 ? (size_t)(mb * 1048576.0) : 0;
-    }
-    return budget;
-}
-
 // One lane per source, and every lane a chain of dependent accesses to its own rows: what hides the latency is the
 // number of wavefronts, not their width.  Narrow workgroups (4 to 64 lanes) until the launch has some 4 096 of them —
 // 20 000 sources are 5 000 four-lane wavefronts, five per SIMD, instead of 313 full ones on a third of the SIMDs; a

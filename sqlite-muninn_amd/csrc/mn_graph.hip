@@ -1,5 +1,5 @@
 // mn_graph.hip — the mn_graph handle: device-resident CSR adjacency (src/graph_csr.h:27-34) uploaded once and shared by
-// the algorithms over it (mn_leiden.hip, mn_centrality.hip), and their common error string.  Host code only.
+// the algorithms over it (mn_leiden.hip, mn_centrality.hip, mn_bfs.hip), and their common error string.  Host code only.
 #include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
 
@@ -184,6 +184,8 @@ extern "C" void mn_graph_destroy(mn_graph *g) {
     (void)hipFree(g->w_out); (void)hipFree(g->w_in);
     if (g->work)
         lei_work_free(g->work);
+    if (g->bfs)
+        bfs_work_free(g->bfs);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->stream) (void)hipStreamDestroy(g->stream);

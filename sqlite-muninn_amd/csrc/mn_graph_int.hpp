@@ -1,9 +1,12 @@
 // mn_graph_int.hpp — what the translation units behind the mn_graph handle share: mn_graph.hip (handle, CSR upload),
-// mn_leiden.hip and mn_centrality.hip.  Host declarations and the kernels' view of the CSR only: device code does not
+// mn_leiden.hip, mn_centrality.hip and mn_bfs.hip.  Host declarations and the kernels' view of the CSR only: device code does not
 // cross a translation unit, every kernel lives in the file that launches it.
 #pragma once
 #include "../../include/muninn_hip.h"
 #include "mn_host.hpp"
+
+#include <algorithm>
+#include <cstdlib>
 
 #define DEVI __device__ __forceinline__
 
@@ -16,6 +19,7 @@ struct DevGraph {
 };
 
 struct LeiWork; // mn_leiden.hip
+struct BfsWork; // mn_bfs.hip
 
 struct mn_graph {
     int device = 0;
@@ -31,6 +35,7 @@ struct mn_graph {
     mn_leiden_stats stats = {};
     std::vector<int> h_off_out, h_off_in; // host copies of the offsets (degrees: list of wide nodes, scratch sizing)
     struct LeiWork *work = nullptr;       // run_leiden's device buffers, allocated on first use and kept
+    struct BfsWork *bfs = nullptr;        // mn_graph_bfs's scratch and the rows of its last call, likewise
 };
 
 inline DevGraph dev_graph_of(const mn_graph *g) { return {g->n, g->off_out, g->tgt_out, g->w_out, g->off_in, g->tgt_in, g->w_in}; }
@@ -46,4 +51,18 @@ inline void graph_note_ms(mn_graph *g) {
         g->last_ms = ms;
 }
 
+// Scratch a call may take: half of what the device has free once `reserve` bytes are set aside, at least 256 MiB — unless
+// the environment variable `env` gives a decimal number of MiB (fractions allowed, <= 0 means 0).
+inline size_t scratch_budget(const char *env, size_t reserve) {
+    size_t budget = (size_t)8 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        budget = std::max<size_t>((size_t)256 << 20, (free_b > reserve ? free_b - reserve : 0) / 2);
+    if (const char *e = getenv(env)) {
+        const double mb = strtod(e, nullptr);
+        budget = mb > 0 ? (size_t)(mb * 1048576.0) : 0;
+    }
+    return budget;
+}
+
 void lei_work_free(LeiWork *w); // mn_leiden.hip: releases and deletes a graph's Leiden workspace (mn_graph_destroy)
+void bfs_work_free(BfsWork *w); // mn_bfs.hip: the same for the traversal's

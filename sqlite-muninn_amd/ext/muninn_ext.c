@@ -6,8 +6,8 @@
  * the first failure aborts with *pzErrMsg set via sqlite3_mprintf.  Registered here: the
  * hot-path surface of SURVEY §8(b) — `hnsw_index` (+ `hnsw0` alias), `node2vec_train`,
  * `graph_leiden` — and §8 f-4's `graph_components` / `graph_pagerank` / `graph_node_betweenness` / `graph_edge_betweenness` /
- * `graph_degree` / `graph_closeness`, and the reference's `muninn_extract_er` (src/llama_er.c), each backed by libmuninn_hip.so
- * (include/muninn_hip.h).
+ * `graph_degree` / `graph_closeness`, the reference's `graph_bfs` (src/graph_tvf.c:230-309; mn_traverse_tvf.c) and its
+ * `muninn_extract_er` (src/llama_er.c), each backed by libmuninn_hip.so (include/muninn_hip.h).
  */
 #include "mn_sqlite_abi.h"
 
@@ -16,6 +16,7 @@ const sqlite3_api_routines *mn_sqlite_api = 0;
 int mn_register_hnsw_module(sqlite3 *db);
 int mn_register_graph_functions(sqlite3 *db) __attribute__((weak));
 int mn_register_graph_tvfs(sqlite3 *db) __attribute__((weak));
+int mn_register_traversal_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_betweenness_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_centrality_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_er_functions(sqlite3 *db) __attribute__((weak));
@@ -41,6 +42,13 @@ int sqlite3_muninn_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
         rc = mn_register_graph_tvfs(db);
         if (rc != SQLITE_OK) {
             *pzErrMsg = sqlite3_mprintf("muninn: failed to register graph TVFs");
+            return rc;
+        }
+    }
+    if (mn_register_traversal_tvfs) {
+        rc = mn_register_traversal_tvfs(db);
+        if (rc != SQLITE_OK) {
+            *pzErrMsg = sqlite3_mprintf("muninn: failed to register traversal TVFs");
             return rc;
         }
     }

@@ -18,6 +18,11 @@ class LeidenStats(C.Structure):
                 ("n_communities", C.c_int), ("device_ms", C.c_double)]
 
 
+class BfsStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("levels", C.c_int64), ("chunks", C.c_int64), ("edges_scanned", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 class N2vParams(C.Structure):
     _fields_ = [("dim", C.c_int), ("p", C.c_double), ("q", C.c_double), ("num_walks", C.c_int), ("walk_length", C.c_int),
                 ("window", C.c_int), ("neg_samples", C.c_int), ("learning_rate", C.c_double), ("epochs", C.c_int),
@@ -69,6 +74,9 @@ GRAPH_SYMBOLS = [
     ("mn_graph_out_lists", C.c_int, [C.c_void_p, _i32p, _i32p]),
     ("mn_graph_closeness", C.c_int, [C.c_void_p, C.c_int, C.c_int, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]),
     ("mn_graph_degree", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mn_graph_bfs", C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                 np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(BfsStats)]),
+    ("mn_graph_bfs_rows", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
     ("mn_graph_pagerank", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_double, C.c_int, C.c_int,
                                     np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), C.POINTER(AlgoStats)]),
     ("mn_graph_components", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(AlgoStats)]),
@@ -173,6 +181,34 @@ class Graph:
             raise MuninnHipError(_gerr())
         return tuple(a[:self.n] for a in out)
 
+    def bfs_batch(self, seeds, max_depth=100, direction="forward"):
+        """run_bfs (src/graph_tvf.c:230-309) from every seed at once → (row_off[len(seeds) + 1] int64, node, depth, parent
+        int32): seed i's rows, in the reference's queue order, are row_off[i] .. row_off[i + 1] - 1; parent is -1 for a
+        seed's own row.  The call's statistics are in self.bfs_stats afterwards."""
+        seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+        row_off = np.zeros(len(seeds) + 1, np.int64)
+        st = BfsStats()
+        d = {"both": 0, "forward": 1, "reverse": 2}[direction]
+        rows = self.L.mn_graph_bfs(self.h, d, len(seeds), seeds.ctypes.data if len(seeds) else None, int(max_depth), row_off,
+                                   C.byref(st))
+        if rows < 0:
+            raise MuninnHipError(_gerr())
+        out = [np.empty(max(rows, 1), np.int32) for _ in range(3)]
+        if self.L.mn_graph_bfs_rows(self.h, *out) != 0:
+            raise MuninnHipError(_gerr())
+        self.bfs_stats = {n: getattr(st, n) for n, _ in BfsStats._fields_}
+        return (row_off,) + tuple(a[:rows] for a in out)
+
+    def bfs(self, seed, max_depth=100, direction="forward"):
+        """graph_bfs's rows from one start node → (node, depth, parent) int32 arrays; self.bfs_stats as for bfs_batch"""
+        return self.bfs_batch([seed], max_depth, direction)[1:]
+
+    def shortest_path_unweighted(self, start, end):
+        """run_shortest_path_bfs (src/graph_tvf.c:472-586): a forward BFS from start whose first-discovery parents are
+        traced back from end on the host → the nodes of the path, start first, or [] when end is not reached."""
+        node, _, parent = self.bfs(start, max_depth=2**31 - 1, direction="forward")
+        return trace_path(node, parent, start, end)
+
     def leiden(self, resolution=1.0, direction="both", mode=LEIDEN_SEQUENTIAL, batch=0):
         """run_leiden → (community[n] int32, Q, stats dict)"""
         comm = np.empty(max(self.n, 1), np.int32)
@@ -183,6 +219,17 @@ class Graph:
         st = LeidenStats()
         self.L.mn_graph_leiden_stats(self.h, C.byref(st))
         return comm[:self.n], q.value, {n: getattr(st, n) for n, _ in LeidenStats._fields_}
+
+
+def trace_path(node, parent, start, end):
+    """the path start .. end through a BFS's (node, parent) rows, or [] when end is not among them"""
+    up = {int(v): int(p) for v, p in zip(node, parent)}
+    if int(end) not in up:
+        return []
+    path = [int(end)]
+    while path[-1] != int(start):
+        path.append(up[path[-1]])
+    return path[::-1]
 
 
 def node2vec_train(off, adj, dim, p=1.0, q=1.0, num_walks=10, walk_length=80, window=5, neg_samples=5, learning_rate=0.025,
