@@ -30,7 +30,7 @@ for key, tag, name in (("leiden_lfr500k_unweighted_sync_default", tu, "unweighte
     ent["fetch_size_kb"], ent["write_size_kb"], ent["traffic_bytes"] = fk, wk, int((2 * fk + wk) * 1024)
     ent["source"] = (f"profiles/r04_leiden_500k_9M_{name}_pmc_summary.csv (round 4, last session: scripts/prof_leiden.sh, separate --pmc passes, "
                      f"{nf} launches of one run_leiden; FETCH_SIZE doubled)")
-    ent["kernel_sources"] = ["mn_leiden.hip", "mn_graph_int.hpp"]
+    ent["kernel_sources"] = ["mn_leiden.hip", "mn_leiden_eval.hpp", "mn_graph_int.hpp"]
     ent["kernel_sources_sha256"] = kernel_sources_sha(ent["kernel_sources"])
     ent["measured_in_round"], ent["measured_at_commit"] = 4, commit
     print(key, ent["traffic_bytes"], nf)

@@ -1,5 +1,6 @@
 // mn_graph.hip — the mn_graph handle: device-resident CSR adjacency (src/graph_csr.h:27-34) uploaded once and shared by
-// the algorithms over it (mn_leiden.hip, mn_centrality.hip, mn_bfs.hip), and their common error string.  Host code only.
+// the algorithms over it (mn_leiden.hip + mn_leiden_eval.hpp, mn_centrality.hip, mn_bfs.hip), and their common error string.
+// Host code only.
 #include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
 

@@ -1,6 +1,7 @@
 // mn_graph_int.hpp — what the translation units behind the mn_graph handle share: mn_graph.hip (handle, CSR upload),
-// mn_leiden.hip, mn_centrality.hip and mn_bfs.hip.  Host declarations and the kernels' view of the CSR only: device code does not
-// cross a translation unit, every kernel lives in the file that launches it.
+// mn_leiden.hip (with mn_leiden_eval.hpp, the device code of its evaluation, included by it alone), mn_centrality.hip and
+// mn_bfs.hip.  Host declarations and the kernels' view of the CSR only: device code does not cross a translation unit, every
+// kernel lives in the file that launches it.
 #pragma once
 #include "../../include/muninn_hip.h"
 #include "mn_host.hpp"

@@ -1,33 +1,28 @@
 // mn_leiden.hip — Leiden community detection (src/graph_community.c:75-429) over device-resident CSR
-// adjacency (src/graph_csr.h:27-34), gfx950.
+// adjacency (src/graph_csr.h:27-34), gfx950: the kernels, their workspace, the bookkeeping between phases, the two phase
+// drivers and the three entry points.  What a wavefront does to evaluate one node is mn_leiden_eval.hpp.
 //
-// The reference sweeps nodes in order and applies every move immediately (:158-228); all arithmetic
-// is f64 and every per-community sum is taken in adjacency-list order.  Device design:
-//   best_move        one wavefront evaluates one node: its edges' (community, weight) pairs are staged
-//                    in LDS in list order; lane e decides whether edge e is the first occurrence of
-//                    its community, sums that community's weights in list order, computes the gain
-//                    expression of :209-210 verbatim in f64 and a max-with-lowest-index reduction
-//                    reproduces the strict `gain > best_gain` first-seen tie rule (:212)
-//   k_leiden_seq     MN_LEIDEN_SEQUENTIAL: ONE wavefront walks v = 0..N-1 with in-place updates
-//                    (agent-scope atomics for label/sum_tot: never a stale L1 line) — community
-//                    assignment and Q bit-identical to the reference
-//   k_leiden_eval_sg / _big / win / apply   MN_LEIDEN_BATCHED: a range of nodes evaluated in parallel against
-//                    frozen state; a mover commits iff it is the smallest-index mover among the
-//                    movers touching its old/target community and its moving neighbours → committed
-//                    moves are pairwise independent, realise exactly their computed gain (Q strictly
-//                    increases) and the result does not depend on execution order.
-//                    The evaluation is a chain of dependent gathers per node (offsets → targets → labels →
-//                    sum_tot), so what it needs is nodes in flight: a wavefront evaluates 64/SG nodes at once in
-//                    SG-lane sub-groups (3.3 KB of LDS per wavefront whatever the largest degree is); the few
-//                    nodes with more than LEI_SG_CAP edges take a whole wavefront each (k_leiden_eval_big over a
-//                    precomputed list).  The movers' per-community tallies are folded into the evaluation.
-// O(N) bookkeeping between phases (renumber :317-331, distinct counts :388-403, sum_tot rebuild
-// :413-416, m :344-350, the per-community accumulation of :128-139) stays on the device for unweighted graphs —
-// every such sum is then a sum of integers below 2^53, exact in any order, so atomics give the reference's bits;
-// first-seen renumbering = atomicMin of the first index per label + a prefix sum over the first-occurrence flags.
-// Weighted graphs keep those sums on the host in the reference's node order (f64 addition is not associative).
+// The reference sweeps nodes in order and applies every move immediately (:158-228).  Schedules:
+//   k_leiden_seq     MN_LEIDEN_SEQUENTIAL: ONE wavefront walks v = 0..N-1 with in-place updates (agent-scope atomics for
+//                    label / sum_tot: never a stale L1 line) — community assignment and Q bit-identical to the reference
+//   k_leiden_eval    MN_LEIDEN_BATCHED: a range of nodes evaluated in parallel against frozen state — a chain of dependent
+//                    gathers per node (offsets → targets → labels → sum_tot), so what it needs is nodes in flight: a wavefront
+//                    evaluates 64/SG nodes at once in SG-lane sub-groups, the few nodes with more than LEI_SG_CAP edges take a
+//                    whole wavefront each (biglist).  The movers' per-community tallies are folded into it (lei_tally).
+//   run_phase_sync   the default: whole-graph sweeps, k_leiden_eval + k_leiden_apply_sync applying EVERY positive-gain mover,
+//                    every LEI_PICKLESS-th sweep only towards smaller community ids; divided by node range over the ranks
+//                    of a communicator
+//   run_phase        rounds of `batch` nodes, k_leiden_eval + k_leiden_win + k_leiden_apply: a mover commits iff it is the
+//                    smallest-index mover among the movers touching its old/target community and its moving neighbours →
+//                    committed moves are pairwise independent, realise exactly their computed gain (Q strictly increases)
+//                    and the result does not depend on execution order.  Also what finishes a synchronous phase that does
+//                    not settle.
+// Weighted graphs: sum_tot receives a round's additions in the reference's order through k_leiden_ops, a stable radix sort
+// and k_leiden_apply_ops (lei_apply_weighted); the apply kernels then only move labels.
+// The O(N) bookkeeping between phases (m :344-350, distinct counts :388-403, renumber :317-331, sum_tot rebuild :413-416, the
+// per-community accumulation of :128-139) comes twice (LeiBook), on the device and on the host.
 // All device buffers are allocated once per graph (LeiWork) and reused by later calls.
-#include "mn_graph_int.hpp"
+#include "mn_leiden_eval.hpp"
 #include "mn_guard.hpp"
 #include "mn_comm.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -39,551 +34,12 @@
 #include <cstdlib>
 #include <cstring>
 
-#define LEI_CAP 1024 // edges of one node staged in LDS; larger nodes use the global scratch path
-#ifndef LEI_SG_CAP
-#define LEI_SG_CAP 64 // sub-group evaluation: edges staged per node (more → the node takes a whole wavefront); power of two
-#endif
-// ints per sub-group: table of 1 << log2h entries (key, count, first position) + counter (4 ints) + 16-bit slot list (one per
-// edge at most).  log2h is LEI_SG_LOG2H (two entries per edge) while most labels are still different — the first sweeps of a
-// phase — and one less afterwards (round 4): the table then takes half the LDS and 32 wavefronts fit a CU instead of 20.  Only
-// communities other than the node's own enter it, at most one per edge, so it cannot overflow at either size.
-#define LEI_SG_AREA_OF(log2h) (3 * (1 << (log2h)) + 4 + LEI_SG_CAP / 2)
 #define LEI_WPB 4 // wavefronts per k_leiden_eval workgroup (at most; power of two)
-#define LEI_SG_LOG2H (LEI_SG_CAP == 32 ? 6 : LEI_SG_CAP == 64 ? 7 : LEI_SG_CAP == 128 ? 8 : 9) // table of 2 * LEI_SG_CAP entries
-
-
-template <bool COH> DEVI int ld_i(const int *p) {
-    if (COH)
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-template <bool COH> DEVI double ld_d(const double *p) {
-    if (COH)
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-
-// Returns the community node v should move to (== its current one if no strictly positive gain).
-// ec/ew/el: staging for the node's edges (community, weight, eligible) in list order — LDS for degree
-// <= LEI_CAP, global scratch otherwise; both 16-byte aligned, capacity rounded up to a multiple of 4.
-template <bool COH>
-DEVI int best_move(const DevGraph &g, int v, const int *label, const double *sum_tot, const double *kdeg, double m,
-                   double resolution, int use_both, const int *elig_part, int *ec, double *ew, unsigned char *el, int lane,
-                   double *dk_out = nullptr, int pickless = 0) {
-    const int o0 = g.off_out[v], d_out = g.off_out[v + 1] - o0;
-    const int i0 = use_both ? g.off_in[v] : 0, d_in = use_both ? g.off_in[v + 1] - i0 : 0;
-    const int d = d_out + d_in;
-    const int d4 = (d + 3) & ~3;
-    const int old = ld_i<COH>(label + v);
-    const int mypart = elig_part ? elig_part[v] : 0;
-    __builtin_amdgcn_wave_barrier();
-    if (COH) {
-        for (int e = lane; e < d4; e += 64) {
-            int c = -2; // padding never matches a community
-            double w = 0.0;
-            unsigned char ok = 0;
-            if (e < d) {
-                int t;
-                if (e < d_out) {
-                    t = g.tgt_out[o0 + e];
-                    w = g.w_out ? g.w_out[o0 + e] : 1.0;
-                } else {
-                    t = g.tgt_in[i0 + (e - d_out)];
-                    w = g.w_in ? g.w_in[i0 + (e - d_out)] : 1.0;
-                }
-                c = ld_i<COH>(label + t);
-                ok = (!elig_part || elig_part[t] == mypart) ? 1 : 0;
-            }
-            ec[e] = c;
-            ew[e] = w;
-            el[e] = ok;
-        }
-    } else {
-        // parallel rounds: four edges per lane in flight — every load unconditional (index clamped to the last edge), the four
-        // targets and weights go out back to back, then the four labels (and partitions): two round trips per 256 edges
-        // instead of two per 64 (the guarded one-edge-per-lane loop above is one s_waitcnt per load)
-        const bool has_w = g.w_out != nullptr || g.w_in != nullptr;
-        for (int e0 = 0; e0 < d4; e0 += 256) {
-            int t[4], c[4], part[4];
-            double w[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int ecl = max(0, min(e0 + j * 64 + lane, d - 1));
-                const bool out = ecl < d_out;
-                t[j] = *(out ? g.tgt_out + o0 + ecl : g.tgt_in + i0 + (ecl - d_out));
-                w[j] = 1.0;
-                if (has_w) {
-                    const double *pw = out ? g.w_out : g.w_in;
-                    w[j] = pw ? pw[(out ? o0 + ecl : i0 + (ecl - d_out))] : 1.0;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                c[j] = label[t[j]];
-            if (elig_part) {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    part[j] = elig_part[t[j]];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int e = e0 + j * 64 + lane;
-                if (e >= d4)
-                    continue;
-                const bool in = e < d;
-                ec[e] = in ? c[j] : -2;
-                ew[e] = in ? w[j] : 0.0;
-                el[e] = in && (!elig_part || part[j] == mypart) ? 1 : 0;
-            }
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    const double k_v = kdeg[v];
-    const int4 *ec4 = reinterpret_cast<const int4 *>(ec);
-    const double2 *ew2 = reinterpret_cast<const double2 *>(ew);
-    const uchar4 *el4 = reinterpret_cast<const uchar4 *>(el);
-    double k_v_to_old = 0.0; // weight_to_community(v, old), :163 — list order
-    for (int q = 0; q < (d4 >> 2); q++) {
-        const int4 cj = ec4[q];
-        const double2 wa = ew2[2 * q], wb = ew2[2 * q + 1];
-        if (cj.x == old) k_v_to_old += wa.x;
-        if (cj.y == old) k_v_to_old += wa.y;
-        if (cj.z == old) k_v_to_old += wb.x;
-        if (cj.w == old) k_v_to_old += wb.y;
-    }
-    const double st_old = ld_d<COH>(sum_tot + old);
-    double best_gain = 0.0;
-    int best = old;
-    for (int base = 0; base < d; base += 64) {
-        const int e = base + lane;
-        const int c = e < d ? ec[e] : -3;
-        bool cand = e < d && el[e] && c != old && !(pickless && c > old);
-        // one pass over the list: the in-order weight sum of community c (weight_to_community, :206) and
-        // "an eligible earlier edge already carries c" (the dedup scan of :173-199)
-        double sacc = 0.0;
-        bool dup = false;
-        for (int q = 0; q < (d4 >> 2); q++) {
-            const int4 cj = ec4[q];
-            const double2 wa = ew2[2 * q], wb = ew2[2 * q + 1];
-            const uchar4 ej = el4[q];
-            const int j = q << 2;
-            if (cj.x == c) { sacc += wa.x; dup |= (j < e) && ej.x; }
-            if (cj.y == c) { sacc += wa.y; dup |= (j + 1 < e) && ej.y; }
-            if (cj.z == c) { sacc += wb.x; dup |= (j + 2 < e) && ej.z; }
-            if (cj.w == c) { sacc += wb.y; dup |= (j + 3 < e) && ej.w; }
-        }
-        cand = cand && !dup;
-        double gain = -1.0, dk = 0.0;
-        if (cand) {
-            const double st_c = ld_d<COH>(sum_tot + c);
-            dk = sacc - k_v_to_old;
-            gain = (sacc - k_v_to_old) / m + resolution * k_v * (st_old - k_v - st_c) / (2.0 * m * m); // :209-210
-            if (!(gain > 0.0))
-                gain = -1.0; // also drops NaN: `gain > best_gain` is false for it
-        }
-        // max gain, lowest lane on ties == first candidate with the strictly largest gain
-        double bg = gain;
-        int bl = lane;
-        for (int mk = 32; mk >= 1; mk >>= 1) {
-            double og = __shfl_xor(bg, mk);
-            int ol = __shfl_xor(bl, mk);
-            if (og > bg || (og == bg && ol < bl)) {
-                bg = og;
-                bl = ol;
-            }
-        }
-        if (bg > best_gain) { // strict: an equal gain in a later chunk does not replace (:212)
-            best_gain = bg;
-            best = __shfl(c, bl);
-            double bdk = __shfl(dk, bl);
-            if (dk_out)
-                *dk_out = bdk;
-        }
-    }
-    return best;
-}
-
-
-// ── unweighted graphs: O(degree) evaluation ──
-// Every weight is 1.0, so weight_to_community(v, c) (:75-90) is the NUMBER of v's edges into c — an integer, exact in
-// any order — and the O(deg · #neighbour communities) rescans of the reference (and of best_move above, which keeps
-// them because weighted sums must be taken in list order) collapse into one pass: each edge is dropped into a small
-// open-addressing table in LDS keyed by community (count, position of the first eligible edge).  The candidates are
-// the occupied entries; the strict-gain first-seen rule (:212) = highest gain, lowest first position.  Same decisions
-// as best_move, bit for bit (the gain expression is evaluated on the same f64 operands).
-#define LEI_EMPTY (-1)
-DEVI unsigned lei_hash(int c, int log2h) { return ((unsigned)c * 2654435761u) >> (32 - log2h); }
-
-// SG lanes (lane = absolute lane, sl = lane % SG) evaluate node v; tk/tc/tp: the group's table of H = 1 << log2h entries
-// everything about node v whose address depends on v alone: requested together, one round trip
-struct LeiHead {
-    int o0, d_out, i0, d_in, old, mypart;
-    double k_v;
-};
-DEVI LeiHead lei_head(const DevGraph &g, int v, const int *label, const double *kdeg, int use_both, const int *elig_part) {
-    LeiHead h;
-    const int o0 = g.off_out[v], o1 = g.off_out[v + 1];
-    const int i0 = g.off_in[use_both ? v : 0], i1 = g.off_in[use_both ? v + 1 : 0]; // (unconditional loads)
-    h.old = label[v];
-    h.mypart = (elig_part ? elig_part : label)[v];
-    h.k_v = kdeg[v];
-    h.o0 = o0;
-    h.d_out = o1 - o0;
-    h.i0 = use_both ? i0 : 0;
-    h.d_in = use_both ? i1 - i0 : 0;
-    return h;
-}
-
-// Lane exchange for the reductions inside a sub-group, without the LDS crossbar (__shfl_xor = ds_bpermute, and the SQ counters of
-// round 4 put this kernel's LDS pipe at ≈ 88 % busy): DPP inside a row of 16 lanes — quad exchanges, then the mirrors (any pairing
-// that ends with every lane holding the row's result serves a commutative, associative reduction) —, shuffles only above 16.
-template <int STEP> DEVI int lei_peer(int v) {
-    if (STEP == 0) return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-    if (STEP == 1) return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);  // quad_perm [2,3,0,1]
-    if (STEP == 2) return __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false); // row_half_mirror
-    if (STEP == 3) return __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false); // row_mirror
-    return __shfl_xor(v, STEP == 4 ? 16 : 32);
-}
-template <int STEP> DEVI double lei_peer(double v) {
-    return __hiloint2double(lei_peer<STEP>(__double2hiint(v)), lei_peer<STEP>(__double2loint(v)));
-}
-struct LeiBest {
-    double gain, dk;
-    int pos, c;
-};
-template <int STEP> DEVI void lei_best_step(LeiBest &b) {
-    const double og = lei_peer<STEP>(b.gain), od = lei_peer<STEP>(b.dk);
-    const int op = lei_peer<STEP>(b.pos), oc = lei_peer<STEP>(b.c);
-    if (og > b.gain || (og == b.gain && op < b.pos)) {
-        b.gain = og;
-        b.pos = op;
-        b.c = oc;
-        b.dk = od;
-    }
-}
-
-// Round 4 (the kernel is bound by the LDS pipe): (i) only the KEYS are cleared, four per ds_write_b128 — whoever inserts a key
-// initialises its count and position (LDS operations of one wavefront execute in program order, and the additions come after the
-// probe loop); (ii) edges into the node's own community, most of them once communities have formed, never touch the table:
-// weight_to_community(v, old) is counted in registers and reduced across the sub-group by DPP; (iii) the closing max-reduction
-// runs on DPP as well.  Same decisions, bit for bit.
-template <int SG>
-DEVI int best_move_hash(const DevGraph &g, const LeiHead &hd, const int *label, const double *sum_tot, double m,
-                        double resolution, const int *elig_part, int *tk, int *tc, int *tp, int *cl, int log2h, int lane,
-                        int sl, double *dk_out, int pickless) {
-    const int H = 1 << log2h;
-    const int o0 = hd.o0, d_out = hd.d_out, i0 = hd.i0, d_in = hd.d_in;
-    const int d = d_out + d_in;
-    const int old = hd.old;
-    const int mypart = elig_part ? hd.mypart : 0;
-    // issued now, consumed after the table is built: this round trip overlaps the targets → labels chain
-    const double k_v = hd.k_v;
-    const double st_old = sum_tot[old];
-    for (int j = 4 * sl; j < H; j += 4 * SG)
-        *reinterpret_cast<int4 *>(tk + j) = make_int4(LEI_EMPTY, LEI_EMPTY, LEI_EMPTY, LEI_EMPTY);
-    // cl[0]: number of occupied entries; then their slots (16-bit), appended by whoever inserts a key — the candidate
-    // scan below visits the occupied entries only (a handful once communities have formed), not the whole table
-    unsigned short *clist = reinterpret_cast<unsigned short *>(cl + 4);
-    if (sl == 0)
-        cl[0] = 0;
-    __builtin_amdgcn_wave_barrier();
-    int n_old = 0; // this lane's edges into the node's own community
-    // Four edges per lane at a time, every load unconditional (index clamped to the last edge): the four targets go out
-    // back to back, then their four labels (and partitions) — two round trips per 4·SG edges instead of two per SG edges.
-    for (int e0 = 0; e0 < d; e0 += 4 * SG) {
-        int t[4], c[4], part[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int ec = min(e0 + j * SG + sl, d - 1);
-            const int *pt = ec < d_out ? g.tgt_out + o0 + ec : g.tgt_in + i0 + (ec - d_out);
-            t[j] = *pt;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            c[j] = label[t[j]];
-        if (elig_part) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                part[j] = elig_part[t[j]];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                part[j] = mypart;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int e = e0 + j * SG + sl;
-            if (e >= d)
-                continue;
-            if (c[j] == old) {
-                n_old++;
-                continue;
-            }
-            // refinement: a target in another phase-1 community carries a refined label that no candidate of this node can
-            // have (a refined community lies inside one phase-1 community, and candidates need an eligible edge) and that is
-            // not `old` either: it changes no count that is looked at — it does not enter the table
-            if (part[j] != mypart)
-                continue;
-            unsigned h = lei_hash(c[j], log2h);
-            for (;;) {
-                int prev = tk[h]; // (a plain read first: most edges find their community already inserted)
-                if (prev == LEI_EMPTY) {
-                    prev = atomicCAS(&tk[h], LEI_EMPTY, c[j]);
-                    if (prev == LEI_EMPTY) {
-                        tc[h] = 0;
-                        tp[h] = 0x7fffffff;
-                        clist[atomicAdd(&cl[0], 1)] = (unsigned short)h;
-                    }
-                }
-                if (prev == LEI_EMPTY || prev == c[j])
-                    break;
-                h = (h + 1) & (H - 1);
-            }
-            atomicAdd(&tc[h], 1);
-            atomicMin(&tp[h], e);
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    n_old += lei_peer<0>(n_old);
-    n_old += lei_peer<1>(n_old);
-    n_old += lei_peer<2>(n_old);
-    n_old += lei_peer<3>(n_old);
-    if (SG > 16)
-        n_old += lei_peer<4>(n_old);
-    if (SG > 32)
-        n_old += lei_peer<5>(n_old);
-    const double k_v_to_old = (double)n_old; // weight_to_community(v, old), :163
-    LeiBest b = {-1.0, 0.0, 0x7fffffff, old};
-    // candidates = the occupied entries, one per lane per pass (max gain, ties to the lowest first position: any order)
-    const int ncand = cl[0];
-    for (int i = sl; i < ncand; i += SG) {
-        const int slot = clist[i];
-        const int c = tk[slot], pos = tp[slot];
-        if (pos == 0x7fffffff || (pickless && c > old))
-            continue;
-        const double sacc = (double)tc[slot];
-        const double st_c = sum_tot[c];
-        double gain = (sacc - k_v_to_old) / m + resolution * k_v * (st_old - k_v - st_c) / (2.0 * m * m); // :209-210
-        if (!(gain > 0.0))
-            continue;
-        if (gain > b.gain || (gain == b.gain && pos < b.pos)) {
-            b.gain = gain;
-            b.pos = pos;
-            b.c = c;
-            b.dk = sacc - k_v_to_old;
-        }
-    }
-    lei_best_step<0>(b);
-    lei_best_step<1>(b);
-    lei_best_step<2>(b);
-    lei_best_step<3>(b);
-    if (SG > 16)
-        lei_best_step<4>(b);
-    if (SG > 32)
-        lei_best_step<5>(b);
-    *dk_out = b.gain > 0.0 ? b.dk : 0.0;
-    return b.gain > 0.0 ? b.c : old;
-}
-
-// ── weighted graphs: O(degree · distinct communities / lanes) evaluation (round 4) ──
-// weight_to_community(v, c) (:75-90) is an f64 sum in LIST ORDER, so the hash-and-count shortcut of the unweighted path does not
-// apply — but the sum does not have to be taken once per EDGE (best_move: every lane sums the community of its own edge, most of
-// them the same few communities: O(degree²) compare-and-add steps, 70 % of a weighted run).  Here every edge is hashed to its
-// community's table slot (as in best_move_hash; the slot remembers the first eligible position), communities are numbered in
-// the order they were inserted, and lane p OWNS community number p: one walk over the staged list in order, adding the weights
-// of the edges whose community number is p — the reference's additions in the reference's order, once per distinct community.
-// Sixteen lanes cover sixteen communities per walk; once communities have formed a node's neighbours lie in a handful.
-DEVI size_t lei_wslots_bytes(int cap, int log2h) { return (size_t)20 * cap + (size_t)10 * (1 << log2h) + 16; }
-template <int SG>
-DEVI int best_move_wslots(const DevGraph &g, const LeiHead &hd, const int *label, const double *sum_tot, double m, double resolution,
-                          const int *elig_part, unsigned char *area, int cap, int log2h, int lane, int sl, double *dk_out,
-                          int pickless) {
-    const int H = 1 << log2h;
-    double *ew = reinterpret_cast<double *>(area);           // [cap] weights in list order (padding 0.0)
-    double *ssum = ew + cap;                                  // [cap] in-order weight sum of community number p
-    int *tk = reinterpret_cast<int *>(ssum + cap);            // [H] community of a slot
-    int *tp = tk + H;                                         // [H] first eligible position
-    unsigned short *tpos = reinterpret_cast<unsigned short *>(tp + H); // [H] slot -> community number
-    unsigned short *spos = tpos + H;                          // [cap] community number -> slot
-    unsigned short *es = spos + cap;                          // [cap] edge -> slot, then edge -> community number (padding 0xFFFF)
-    int *cnt = reinterpret_cast<int *>(es + cap);
-    const int o0 = hd.o0, d_out = hd.d_out, i0 = hd.i0, d_in = hd.d_in;
-    const int d = d_out + d_in;
-    const int d4 = (d + 3) & ~3;
-    const int old = hd.old;
-    const int mypart = elig_part ? hd.mypart : 0;
-    const double k_v = hd.k_v;
-    *dk_out = 0.0;
-    if (d == 0)
-        return old;
-    const double st_old = sum_tot[old];
-    for (int j = 4 * sl; j < H; j += 4 * SG)
-        *reinterpret_cast<int4 *>(tk + j) = make_int4(LEI_EMPTY, LEI_EMPTY, LEI_EMPTY, LEI_EMPTY);
-    if (sl == 0)
-        cnt[0] = 0;
-    __builtin_amdgcn_wave_barrier();
-    for (int e0 = 0; e0 < d4; e0 += 4 * SG) { // four edges per lane in flight: targets + weights, then labels (+ partitions)
-        int t[4], c[4], part[4];
-        double w[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int ecl = min(e0 + j * SG + sl, d - 1);
-            const bool out = ecl < d_out;
-            t[j] = *(out ? g.tgt_out + o0 + ecl : g.tgt_in + i0 + (ecl - d_out));
-            const double *pw = out ? g.w_out : g.w_in;
-            w[j] = pw ? pw[out ? o0 + ecl : i0 + (ecl - d_out)] : 1.0;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            c[j] = label[t[j]];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            part[j] = elig_part ? elig_part[t[j]] : mypart;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int e = e0 + j * SG + sl;
-            if (e >= d4)
-                continue;
-            if (e >= d) {
-                ew[e] = 0.0;
-                es[e] = 0xFFFF;
-                continue;
-            }
-            ew[e] = w[j];
-            unsigned h = lei_hash(c[j], log2h);
-            for (;;) {
-                int prev = tk[h];
-                if (prev == LEI_EMPTY) {
-                    prev = atomicCAS(&tk[h], LEI_EMPTY, c[j]);
-                    if (prev == LEI_EMPTY) { // (the inserter numbers the community; LDS operations of a wavefront run in order)
-                        const int p = atomicAdd(&cnt[0], 1);
-                        tpos[h] = (unsigned short)p;
-                        spos[p] = (unsigned short)h;
-                        tp[h] = 0x7fffffff;
-                    }
-                }
-                if (prev == LEI_EMPTY || prev == c[j])
-                    break;
-                h = (h + 1) & (H - 1);
-            }
-            es[e] = (unsigned short)h;
-            if (part[j] == mypart)
-                atomicMin(&tp[h], e);
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    for (int e = sl; e < d; e += SG) // slot -> community number
-        es[e] = tpos[es[e]];
-    __builtin_amdgcn_wave_barrier();
-    const int ncomm = cnt[0];
-    const ushort4 *es4 = reinterpret_cast<const ushort4 *>(es);
-    const double2 *ew2 = reinterpret_cast<const double2 *>(ew);
-    for (int p0 = 0; p0 < ncomm; p0 += SG) { // lane p walks the list for community number p: list-order f64 sum (:75-90)
-        const int p = p0 + sl;
-        const unsigned short my = p < ncomm ? (unsigned short)p : (unsigned short)0xFFFE;
-        double acc = 0.0;
-        for (int q = 0; q < (d4 >> 2); q++) {
-            const ushort4 e4 = es4[q];
-            const double2 wa = ew2[2 * q], wb = ew2[2 * q + 1];
-            if (e4.x == my) acc += wa.x;
-            if (e4.y == my) acc += wa.y;
-            if (e4.z == my) acc += wb.x;
-            if (e4.w == my) acc += wb.y;
-        }
-        if (p < ncomm)
-            ssum[p] = acc;
-    }
-    __builtin_amdgcn_wave_barrier();
-    double k_v_to_old = 0.0; // weight_to_community(v, old), :163
-    {
-        unsigned h = lei_hash(old, log2h);
-        for (int probe = 0; probe < H; probe++) {
-            const int key = tk[h];
-            if (key == old) {
-                k_v_to_old = ssum[tpos[h]];
-                break;
-            }
-            if (key == LEI_EMPTY)
-                break;
-            h = (h + 1) & (H - 1);
-        }
-    }
-    LeiBest b = {-1.0, 0.0, 0x7fffffff, old};
-    for (int p = sl; p < ncomm; p += SG) { // max gain, ties to the lowest first eligible position = the first-seen rule (:212)
-        const int h = spos[p];
-        const int c = tk[h], pos = tp[h];
-        if (c == old || pos == 0x7fffffff || (pickless && c > old))
-            continue;
-        const double sacc = ssum[p];
-        const double st_c = sum_tot[c];
-        const double gain = (sacc - k_v_to_old) / m + resolution * k_v * (st_old - k_v - st_c) / (2.0 * m * m); // :209-210
-        if (!(gain > 0.0))
-            continue;
-        if (gain > b.gain || (gain == b.gain && pos < b.pos)) {
-            b.gain = gain;
-            b.pos = pos;
-            b.c = c;
-            b.dk = sacc - k_v_to_old;
-        }
-    }
-    lei_best_step<0>(b);
-    lei_best_step<1>(b);
-    lei_best_step<2>(b);
-    lei_best_step<3>(b);
-    if (SG > 16)
-        lei_best_step<4>(b);
-    if (SG > 32)
-        lei_best_step<5>(b);
-    *dk_out = b.gain > 0.0 ? b.dk : 0.0;
-    return b.gain > 0.0 ? b.c : old;
-}
-
-struct LeiArgs {
-    DevGraph g;
-    int *label;
-    double *sum_tot;
-    const double *kdeg;
-    double m, resolution;
-    int use_both;
-    const int *elig_part; // refinement: phase-1 partition; null for local moving
-    int *scratch_c;       // global scratch for nodes with more than LEI_CAP edges: [blocks][max_deg]
-    double *scratch_w;
-    unsigned char *scratch_e;
-    int max_deg;
-    int *out; // [0] moves [1] sweeps
-    int max_sweeps;
-    // batched
-    int b0, b1;
-    int *dec, *cmin;
-    unsigned char *win;
-    unsigned char *mv;           // [round slot] 1 = the node wants to move (k_leiden_win scans these instead of dec + label)
-    double *dk;
-    unsigned long long *Jq, *Lq; // fixed-point (2^20) tallies of the movers' degrees per community
-    int apply_on_device;         // 0: weighted graph → the host applies winners in node order
-    int lds_cap;                 // k_leiden_eval_big: edges staged in LDS per node (multiple of 16, ≤ LEI_CAP)
-    const int *biglist;          // nodes with more than LEI_SG_CAP edges, ascending
-    const long long *bigoff;     // [biglist index] offset of the node's region in scratch_c/w/e (nodes with more than LEI_CAP edges)
-    int big0, big1;              // the slice of biglist inside [b0, b1)
-    int parity;                  // round parity: out[1 + parity] counts this round's safe winners
-    int big_log2h;               // table size of a wide node: 2^big_log2h >= lds_cap (one entry per edge at most, so it may fill up)
-    int sync;                    // 1: whole-graph synchronous sweep — every positive-gain mover applies, no tallies (k_leiden_apply_sync)
-    int pickless;                // this sweep only allows moves to a community with a smaller id
-    int sg_log2h;                // log2 of a sub-group's table size (unweighted): LEI_SG_LOG2H, or one less once labels have merged
-};
-
-#define LEI_FX 1048576.0
 #define LEI_GROW 4       // tail rule of the batched schedule: round size factor ...
 #define LEI_GROW_DIV 256 // ... once a sweep commits fewer than N / 256 moves
 #define LEI_GROW_MAX 64  // (upper bound of the MN_LEIDEN_GROW tuning knob)
-DEVI unsigned long long fx_up(double k) { return (unsigned long long)ceil(k * LEI_FX); }
 
-DEVI int node_degree(const LeiArgs &a, int v) {
-    return a.g.off_out[v + 1] - a.g.off_out[v] + (a.use_both ? a.g.off_in[v + 1] - a.g.off_in[v] : 0);
-}
-
+// ───────────────────────── kernels ─────────────────────────
 __global__ void __launch_bounds__(64) k_leiden_seq(LeiArgs a) {
     __shared__ __align__(16) double lds_w[LEI_CAP];
     __shared__ __align__(16) int lds_c[LEI_CAP];
@@ -623,26 +79,11 @@ __global__ void __launch_bounds__(64) k_leiden_seq(LeiArgs a) {
     }
 }
 
-// a mover's tallies: smallest mover index per touched community, and the movers' degrees leaving / joining it
-DEVI void lei_tally(const LeiArgs &a, int v, int old, int best, double dk) {
-    a.dec[v - a.b0] = best;
-    if (a.sync) // synchronous sweep: the decision is all k_leiden_apply_sync needs
-        return;
-    a.dk[v - a.b0] = dk;
-    a.mv[v - a.b0] = best != old;
-    if (best == old)
-        return;
-    atomicMin(a.cmin + old, v);
-    atomicMin(a.cmin + best, v);
-    const unsigned long long q = fx_up(a.kdeg[v]);
-    atomicAdd(a.Lq + old, q);
-    atomicAdd(a.Jq + best, q);
-}
-
 // One launch evaluates a whole round: blocks [0, nsmall) take 64/SG nodes each in SG-lane sub-groups (nodes with more
 // than LEI_SG_CAP edges are skipped there), blocks [nsmall, nsmall + big1 - big0) take one such wide node each
-// (biglist).  HASH = unweighted graph → best_move_hash; otherwise the list-order f64 sums of best_move(_sg).
-// Dynamic LDS: max(sub-group area, wide-node area) — sized by the host (lei_eval_lds).
+// (biglist).  HASH = unweighted graph → best_move_hash; otherwise the list-order f64 sums of best_move_wslots; a wide node
+// past lds_cap edges: best_move in global scratch.  Dynamic LDS: max(sub-group area, wide-node area) — sized by the host
+// (lei_eval_lds).
 template <int SG, bool HASH>
 __global__ void __launch_bounds__(64 * LEI_WPB) k_leiden_eval(LeiArgs a, int nsmall, unsigned wave_lds) {
     // LEI_WPB independent wavefronts per workgroup (no workgroup barrier anywhere): a quarter of the workgroups to dispatch
@@ -657,27 +98,22 @@ __global__ void __launch_bounds__(64 * LEI_WPB) k_leiden_eval(LeiArgs a, int nsm
         if (v >= a.b1)
             return;
         double dk = 0.0;
-        int best, old;
+        int best;
+        const LeiHead hd = lei_head(a.g, v, a.label, a.kdeg, a.use_both, a.elig_part);
+        if (hd.d_out + hd.d_in > LEI_SG_CAP)
+            return;
         if (HASH) {
-            const LeiHead hd = lei_head(a.g, v, a.label, a.kdeg, a.use_both, a.elig_part);
-            if (hd.d_out + hd.d_in > LEI_SG_CAP)
-                return;
-            old = hd.old;
             const int H = 1 << a.sg_log2h;
             int *tk = reinterpret_cast<int *>(lei_smem) + grp * LEI_SG_AREA_OF(a.sg_log2h);
             best = best_move_hash<SG>(a.g, hd, a.label, a.sum_tot, a.m, a.resolution, a.elig_part, tk, tk + H, tk + 2 * H, tk + 3 * H,
                                       a.sg_log2h, lane, sl, &dk, a.pickless);
         } else {
-            const LeiHead hd = lei_head(a.g, v, a.label, a.kdeg, a.use_both, a.elig_part);
-            if (hd.d_out + hd.d_in > LEI_SG_CAP)
-                return;
-            old = hd.old;
             unsigned char *area = lei_smem + (size_t)grp * lei_wslots_bytes(LEI_SG_CAP, LEI_SG_LOG2H - 1);
             best = best_move_wslots<SG>(a.g, hd, a.label, a.sum_tot, a.m, a.resolution, a.elig_part, area, LEI_SG_CAP, LEI_SG_LOG2H - 1,
                                         lane, sl, &dk, a.pickless);
         }
         if (sl == 0)
-            lei_tally(a, v, old, best, dk);
+            lei_tally(a, v, hd.old, best, dk);
         return;
     }
     const int bi = vblock - nsmall;
@@ -707,17 +143,6 @@ __global__ void __launch_bounds__(64 * LEI_WPB) k_leiden_eval(LeiArgs a, int nsm
     }
     if (lane == 0)
         lei_tally(a, v, a.label[v], best, dk);
-}
-
-static size_t lei_wslots_bytes_h(int cap, int log2h) { return (size_t)20 * cap + (size_t)10 * ((size_t)1 << log2h) + 16; }
-// LDS bytes of one k_leiden_eval workgroup
-static size_t lei_eval_lds(int sg, bool hash, int lds_cap, int big_log2h, int sg_log2h) {
-    const int ng = 64 / sg;
-    const size_t small = hash ? (size_t)ng * LEI_SG_AREA_OF(sg_log2h) * sizeof(int) : (size_t)ng * lei_wslots_bytes_h(LEI_SG_CAP, LEI_SG_LOG2H - 1);
-    // table (3 ints per entry) + occupied-entry list: a counter (16 B) and one 16-bit slot per edge
-    const size_t big = hash ? (size_t)3 * ((size_t)1 << big_log2h) * sizeof(int) + 16 + (((size_t)lds_cap * 2 + 15) & ~(size_t)15)
-                            : lei_wslots_bytes_h(lds_cap, big_log2h);
-    return small > big ? small : big;
 }
 
 // movers whose smaller-index neighbours in the round do not move ("free"), gain re-checked in the worst order of
@@ -837,6 +262,7 @@ __global__ void __launch_bounds__(256) k_leiden_apply_sync(LeiArgs a) {
             applied = 1;
         }
     }
+    // (k_leiden_apply's epilogue, written out in both: a helper taking the counter by reference compiles to other instructions)
     const unsigned long long ba = __ballot(applied);
     if (ba && (threadIdx.x & 63) == __ffsll((long long)ba) - 1)
         atomicAdd(&blk_moves, __popcll(ba));
@@ -910,177 +336,7 @@ __global__ void k_w2c_self(DevGraph g, int use_both, const int *label, double *o
     out[v] = s;
 }
 
-// ───────────────────────── host ─────────────────────────
-
-// ───────────────────────── run_leiden workspace (one per graph, reused) ─────────────────────────
-
-struct LeiWork {
-    int n = 0, batch_cap = 0, big_mode = -1;
-    int *label = nullptr, *refined = nullptr, *out = nullptr, *dec = nullptr, *cmin = nullptr, *sc = nullptr,
-        *first = nullptr, *flag = nullptr, *rank = nullptr, *biglist = nullptr, *counts = nullptr;
-    unsigned char *win = nullptr, *mv = nullptr, *se = nullptr;
-    double *sum_tot = nullptr, *kdeg = nullptr, *tmp = nullptr, *sw = nullptr, *dk = nullptr, *scal = nullptr,
-           *s_in = nullptr;
-    unsigned long long *Jq = nullptr, *Lq = nullptr;
-    long long *bigoff = nullptr;
-    // weighted graphs: the round's operations keyed by community, their stable sort (k_leiden_ops / k_leiden_apply_ops)
-    int *okeys = nullptr, *okeys_s = nullptr, *oiota = nullptr, *oops_s = nullptr;
-    void *osort_tmp = nullptr;
-    size_t osort_bytes = 0;
-    int osort_bits = 0, ocap = 0;
-    size_t scratch_need = 0, scratch_have = 0; // entries: one region per node with more than LEI_CAP edges
-    void *scan_tmp = nullptr;
-    size_t scan_bytes = 0;
-    int *h_out = nullptr;          // pinned: per-sweep move counts read back without stalling the launch queue
-    hipEvent_t ev_rd[2] = {nullptr, nullptr};
-    std::vector<int> h_big; // nodes with more than LEI_SG_CAP edges (for big_mode = use_both)
-    void release() {
-        void *ps[] = {label, refined, out, dec, cmin, sc, first, flag, rank, biglist, counts, win, mv, se, sum_tot, kdeg,
-                      tmp, sw, dk, scal, s_in, Jq, Lq, scan_tmp, bigoff, okeys, okeys_s, oiota, oops_s, osort_tmp};
-        for (void *q : ps)
-            (void)hipFree(q);
-        if (h_out)
-            (void)hipHostFree(h_out);
-        for (hipEvent_t e : ev_rd)
-            if (e)
-                (void)hipEventDestroy(e);
-    }
-};
-
-void lei_work_free(LeiWork *w) {
-    w->release();
-    delete w;
-}
-
-static int renumber(std::vector<int> &c) { // :317-331
-    const int N = (int)c.size();
-    std::vector<int> map((size_t)N, -1);
-    int next = 0;
-    for (int i = 0; i < N; i++) {
-        if (map[c[i]] == -1)
-            map[c[i]] = next++;
-        c[i] = map[c[i]];
-    }
-    return next;
-}
-
-static int distinct(const std::vector<int> &c) {
-    std::vector<unsigned char> seen(c.size(), 0);
-    int n = 0;
-    for (int x : c)
-        if (!seen[x]) {
-            seen[x] = 1;
-            n++;
-        }
-    return n;
-}
-
-template <typename T> static int wmalloc(T **p, size_t n) {
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    GCHK(hipMalloc(p, (n ? n : 1) * sizeof(T)));
-    return 0;
-}
-
-__global__ void k_iota(int *p, int n);
-
-// (re)size the workspace for this call; everything is kept for the next one
-static int lei_prepare(mn_graph *g, int mode, int batch, int use_both, int max_deg) {
-    if (!g->work)
-        g->work = new LeiWork();
-    LeiWork &w = *g->work;
-    if (!w.h_out) {
-        GCHK(hipHostMalloc(&w.h_out, 8 * sizeof(int)));
-        GCHK(hipEventCreateWithFlags(&w.ev_rd[0], hipEventDisableTiming));
-        GCHK(hipEventCreateWithFlags(&w.ev_rd[1], hipEventDisableTiming));
-    }
-    const int N = g->n;
-    hipStream_t st = g->stream;
-    if (w.n != N) {
-        if (wmalloc(&w.label, (size_t)N) || wmalloc(&w.refined, (size_t)N) || wmalloc(&w.sum_tot, (size_t)N) ||
-            wmalloc(&w.kdeg, (size_t)N) || wmalloc(&w.tmp, (size_t)N + 64) || wmalloc(&w.out, 16) || wmalloc(&w.cmin, (size_t)N) ||
-            wmalloc(&w.Jq, (size_t)N) || wmalloc(&w.Lq, (size_t)N) || wmalloc(&w.first, (size_t)N) || wmalloc(&w.flag, (size_t)N) ||
-            wmalloc(&w.rank, (size_t)N) || wmalloc(&w.counts, 8) || wmalloc(&w.scal, 8) || wmalloc(&w.s_in, (size_t)N))
-            return -1;
-        size_t bytes = 0;
-        if (rocprim::exclusive_scan(nullptr, bytes, w.flag, w.rank, 0, (size_t)N, rocprim::plus<int>(), st) != hipSuccess) {
-            gset_err("rocprim::exclusive_scan (size query) failed");
-            return -1;
-        }
-        if (w.scan_tmp)
-            (void)hipFree(w.scan_tmp);
-        w.scan_tmp = nullptr;
-        GCHK(hipMalloc(&w.scan_tmp, bytes ? bytes : 16));
-        w.scan_bytes = bytes;
-        w.n = N;
-        w.big_mode = -1;
-    }
-    // every round leaves the tallies clean (k_leiden_apply); a call that failed half-way may not have
-    GCHK(hipMemsetAsync(w.cmin, 0x7f, (size_t)N * sizeof(int), st)); // 0x7f7f7f7f > any node index
-    GCHK(hipMemsetAsync(w.Jq, 0, (size_t)N * sizeof(unsigned long long), st));
-    GCHK(hipMemsetAsync(w.Lq, 0, (size_t)N * sizeof(unsigned long long), st));
-    if (w.big_mode != use_both) { // nodes the sub-group kernel leaves to the one-wavefront-per-node kernel
-        w.h_big.clear();
-        std::vector<long long> h_off;
-        size_t need = 0; // scratch entries: Σ degree (int4-aligned) over the nodes that do not fit in LDS — at most 2E + 4N
-        for (int v = 0; v < N; v++) {
-            const int d = g->h_off_out[v + 1] - g->h_off_out[v] + (use_both ? g->h_off_in[v + 1] - g->h_off_in[v] : 0);
-            if (d > LEI_SG_CAP) {
-                w.h_big.push_back(v);
-                h_off.push_back((long long)need);
-                if (d > LEI_CAP)
-                    need += ((size_t)d + 7) & ~(size_t)3;
-            }
-        }
-        w.scratch_need = need;
-        if (wmalloc(&w.biglist, w.h_big.size()) || wmalloc(&w.bigoff, w.h_big.size()))
-            return -1;
-        if (!w.h_big.empty()) {
-            GCHK(hipMemcpyAsync(w.biglist, w.h_big.data(), w.h_big.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            GCHK(hipMemcpyAsync(w.bigoff, h_off.data(), h_off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-            GCHK(hipStreamSynchronize(st)); // (h_off is a local)
-        }
-        w.big_mode = use_both;
-    }
-    if (mode == MN_LEIDEN_BATCHED && batch > w.batch_cap) {
-        if (wmalloc(&w.dec, (size_t)batch + 64) || wmalloc(&w.dk, (size_t)batch) || wmalloc(&w.win, (size_t)batch) || wmalloc(&w.mv, (size_t)batch))
-            return -1;
-        w.batch_cap = batch;
-    }
-    if (mode == MN_LEIDEN_BATCHED && g->weighted && (batch > w.ocap || !w.okeys)) {
-        const size_t n_ops = (size_t)2 * batch;
-        if (wmalloc(&w.okeys, n_ops) || wmalloc(&w.okeys_s, n_ops) || wmalloc(&w.oiota, n_ops) || wmalloc(&w.oops_s, n_ops))
-            return -1;
-        hipLaunchKernelGGL(k_iota, dim3((unsigned)((n_ops + 255) / 256)), dim3(256), 0, st, w.oiota, (int)n_ops);
-        w.osort_bits = 1;
-        while (w.osort_bits < 31 && (1ll << w.osort_bits) <= (long long)N) // keys 0..N (N = "not a winner")
-            w.osort_bits++;
-        size_t bytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, bytes, w.okeys, w.okeys_s, w.oiota, w.oops_s, n_ops, 0, w.osort_bits, st) != hipSuccess) {
-            gset_err("rocprim::radix_sort_pairs (size query) failed");
-            return -1;
-        }
-        if (w.osort_tmp)
-            (void)hipFree(w.osort_tmp);
-        w.osort_tmp = nullptr;
-        GCHK(hipMalloc(&w.osort_tmp, bytes ? bytes : 16));
-        w.osort_bytes = bytes;
-        w.ocap = batch;
-    }
-    // global scratch for nodes whose edges do not fit in LDS: the sequential kernel reuses one region of max_deg entries,
-    // the batched rounds give every such node its own (bigoff) — sized by those nodes' degrees, not by the round
-    const size_t want = std::max<size_t>(w.scratch_need, (size_t)max_deg);
-    if (max_deg > LEI_CAP && want > w.scratch_have) {
-        if (wmalloc(&w.sc, want) || wmalloc(&w.sw, want) || wmalloc(&w.se, want))
-            return -1;
-        w.scratch_have = want;
-    }
-    return 0;
-}
-
-// ───────────────────────── device bookkeeping (unweighted graphs: all sums are exact integers) ─────────────────────────
-
+// the device bookkeeping's (unweighted graphs: all sums are exact integers)
 __global__ void k_iota(int *p, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
@@ -1129,31 +385,133 @@ __global__ void k_scatter_add(const int *label, const double *val, int n, double
         atomicAdd(acc + label[i], val[i]);
 }
 
-// distinct labels of `label` → counts[slot] (device), leaves first[] / flag[] describing `label`
-static int dev_distinct(mn_graph *g, const int *label, int slot) {
-    LeiWork &w = *g->work;
-    const int N = g->n, nb = (N + 255) / 256;
-    hipStream_t st = g->stream;
-    GCHK(hipMemsetAsync(w.first, 0x7f, (size_t)N * sizeof(int), st));
-    GCHK(hipMemsetAsync(w.counts + slot, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_first_seen, dim3(nb), dim3(256), 0, st, label, N, w.first);
-    hipLaunchKernelGGL(k_first_flag, dim3(nb), dim3(256), 0, st, label, w.first, N, w.flag, w.counts + slot);
-    return 0;
-}
-// renumber `label` in place in first-seen order (first[] / flag[] must describe it: dev_distinct)
-static int dev_renumber(mn_graph *g, int *label) {
-    LeiWork &w = *g->work;
-    const int N = g->n, nb = (N + 255) / 256;
-    hipStream_t st = g->stream;
-    size_t bytes = w.scan_bytes;
-    if (rocprim::exclusive_scan(w.scan_tmp, bytes, w.flag, w.rank, 0, (size_t)N, rocprim::plus<int>(), st) != hipSuccess) {
-        gset_err("rocprim::exclusive_scan failed");
-        return -1;
+// ───────────────────────── run_leiden workspace (one per graph, reused) ─────────────────────────
+template <typename T> struct LeiBuf { // a device array the workspace owns; its contents are undefined after alloc
+    T *p = nullptr;
+    size_t cap = 0; // entries asked for
+    LeiBuf() = default;
+    LeiBuf(const LeiBuf &) = delete;
+    ~LeiBuf() { (void)hipFree(p); }
+    operator T *() const { return p; }
+    int alloc(size_t n) { // exactly n entries
+        (void)hipFree(p);
+        p = nullptr, cap = 0;
+        GCHK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
+        cap = n;
+        return 0;
     }
-    hipLaunchKernelGGL(k_relabel, dim3(nb), dim3(256), 0, st, label, w.first, w.rank, N);
+    int fit(size_t n) { return p && n <= cap ? 0 : alloc(n); } // at least n entries: what there is, or exactly n
+};
+
+struct LeiWork {
+    int n = 0, big_mode = -1; // what the per-node arrays and biglist / bigoff were made for: node count, use_both
+    LeiBuf<int> label, refined, out, dec, cmin, sc, first, flag, rank, biglist, counts;
+    LeiBuf<unsigned char> win, mv, se;
+    LeiBuf<double> sum_tot, kdeg, tmp, sw, dk, scal, s_in;
+    LeiBuf<unsigned long long> Jq, Lq;
+    LeiBuf<long long> bigoff;
+    // weighted graphs: the round's operations keyed by community, their stable sort (k_leiden_ops / k_leiden_apply_ops)
+    LeiBuf<int> okeys, okeys_s, oiota, oops_s;
+    LeiBuf<unsigned char> osort_tmp, scan_tmp; // rocPRIM's
+    int osort_bits = 0;
+    size_t osort_bytes = 0, scan_bytes = 0, scratch_need = 0; // scratch entries: a region per node with more than LEI_CAP edges
+    int *h_out = nullptr;    // pinned: per-sweep move counts read back without stalling the launch queue
+    hipEvent_t ev_rd[2] = {nullptr, nullptr};
+    std::vector<int> h_big; // nodes with more than LEI_SG_CAP edges (for big_mode = use_both)
+    ~LeiWork() {
+        (void)hipHostFree(h_out);
+        for (hipEvent_t e : ev_rd)
+            if (e)
+                (void)hipEventDestroy(e);
+    }
+};
+
+void lei_work_free(LeiWork *w) { delete w; }
+
+// (re)size the workspace for this call; everything is kept for the next one
+static int lei_prepare(mn_graph *g, int mode, int batch, int use_both, int max_deg) {
+    if (!g->work)
+        g->work = new LeiWork();
+    LeiWork &w = *g->work;
+    if (!w.h_out) {
+        GCHK(hipHostMalloc(&w.h_out, 8 * sizeof(int)));
+        GCHK(hipEventCreateWithFlags(&w.ev_rd[0], hipEventDisableTiming));
+        GCHK(hipEventCreateWithFlags(&w.ev_rd[1], hipEventDisableTiming));
+    }
+    const int N = g->n;
+    const size_t n = (size_t)N;
+    hipStream_t st = g->stream;
+    if (w.n != N) {
+        if (w.label.alloc(n) || w.refined.alloc(n) || w.sum_tot.alloc(n) || w.kdeg.alloc(n) || w.tmp.alloc(n + 64) || w.out.alloc(16) ||
+            w.cmin.alloc(n) || w.Jq.alloc(n) || w.Lq.alloc(n) || w.first.alloc(n) || w.flag.alloc(n) || w.rank.alloc(n) ||
+            w.counts.alloc(8) || w.scal.alloc(8) || w.s_in.alloc(n))
+            return -1;
+        size_t bytes = 0;
+        if (rocprim::exclusive_scan(nullptr, bytes, w.flag.p, w.rank.p, 0, n, rocprim::plus<int>(), st) != hipSuccess) {
+            gset_err("rocprim::exclusive_scan (size query) failed");
+            return -1;
+        }
+        if (w.scan_tmp.alloc(bytes ? bytes : 16))
+            return -1;
+        w.scan_bytes = bytes;
+        w.n = N;
+        w.big_mode = -1;
+    }
+    // every round leaves the tallies clean (k_leiden_apply); a call that failed half-way may not have
+    GCHK(hipMemsetAsync(w.cmin, 0x7f, n * sizeof(int), st)); // 0x7f7f7f7f > any node index
+    GCHK(hipMemsetAsync(w.Jq, 0, n * sizeof(unsigned long long), st));
+    GCHK(hipMemsetAsync(w.Lq, 0, n * sizeof(unsigned long long), st));
+    if (w.big_mode != use_both) { // nodes the sub-group evaluation leaves to a wavefront of their own
+        w.h_big.clear();
+        std::vector<long long> h_off;
+        size_t need = 0; // scratch entries: Σ degree (int4-aligned) over the nodes that do not fit in LDS — at most 2E + 4N
+        for (int v = 0; v < N; v++) {
+            const int d = g->h_off_out[v + 1] - g->h_off_out[v] + (use_both ? g->h_off_in[v + 1] - g->h_off_in[v] : 0);
+            if (d > LEI_SG_CAP) {
+                w.h_big.push_back(v);
+                h_off.push_back((long long)need);
+                if (d > LEI_CAP)
+                    need += ((size_t)d + 7) & ~(size_t)3;
+            }
+        }
+        w.scratch_need = need;
+        if (w.biglist.alloc(w.h_big.size()) || w.bigoff.alloc(w.h_big.size()))
+            return -1;
+        if (!w.h_big.empty()) {
+            GCHK(hipMemcpyAsync(w.biglist, w.h_big.data(), w.h_big.size() * sizeof(int), hipMemcpyHostToDevice, st));
+            GCHK(hipMemcpyAsync(w.bigoff, h_off.data(), h_off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+            GCHK(hipStreamSynchronize(st)); // (h_off is a local)
+        }
+        w.big_mode = use_both;
+    }
+    const size_t nb = (size_t)batch, n_ops = 2 * nb; // a round's decisions, grown to the largest round asked for so far
+    if (mode == MN_LEIDEN_BATCHED && (w.dec.fit(nb + 64) || w.dk.fit(nb) || w.win.fit(nb) || w.mv.fit(nb)))
+        return -1;
+    if (mode == MN_LEIDEN_BATCHED && g->weighted && n_ops > w.okeys.cap) {
+        w.osort_bits = 1;
+        while (w.osort_bits < 31 && (1ll << w.osort_bits) <= (long long)N) // keys 0..N (N = "not a winner")
+            w.osort_bits++;
+        size_t bytes = 0; // (a size query reads none of the arrays)
+        if (rocprim::radix_sort_pairs(nullptr, bytes, w.okeys.p, w.okeys_s.p, w.oiota.p, w.oops_s.p, n_ops, 0, w.osort_bits, st) != hipSuccess) {
+            gset_err("rocprim::radix_sort_pairs (size query) failed");
+            return -1;
+        }
+        // okeys last: its capacity is what brings a call here, so a failure half-way is made good by the next call
+        if (w.osort_tmp.alloc(bytes ? bytes : 16) || w.okeys_s.alloc(n_ops) || w.oiota.alloc(n_ops) || w.oops_s.alloc(n_ops) ||
+            w.okeys.alloc(n_ops))
+            return -1;
+        w.osort_bytes = bytes;
+        hipLaunchKernelGGL(k_iota, dim3((unsigned)((n_ops + 255) / 256)), dim3(256), 0, st, w.oiota, (int)n_ops);
+    }
+    // global scratch for nodes whose edges do not fit in LDS: the sequential kernel reuses one region of max_deg entries,
+    // the batched rounds give every such node its own (bigoff) — sized by those nodes' degrees, not by the round
+    const size_t want = std::max<size_t>(w.scratch_need, (size_t)max_deg);
+    if (max_deg > LEI_CAP && (w.sc.fit(want) || w.sw.fit(want) || w.se.fit(want)))
+        return -1;
     return 0;
 }
 
+// ───────────────────────── phase drivers ─────────────────────────
 // the tail rule's constants; MN_LEIDEN_GROW="factor,divisor" is a tuning knob (the oracle reads ORC_LEI_GROW the same way:
 // other values give another — equally valid — schedule, so parity holds only when both sides are set alike)
 static void lei_grow_setting(int *grow, int *grow_div) {
@@ -1163,6 +521,16 @@ static void lei_grow_setting(int *grow, int *grow_div) {
         sscanf(e, "%d,%d", grow, grow_div);
     *grow = std::min(std::max(*grow, 1), LEI_GROW_MAX);
     *grow_div = std::max(*grow_div, 1);
+}
+
+// LDS bytes of one k_leiden_eval wavefront
+static size_t lei_eval_lds(int sg, bool hash, int lds_cap, int big_log2h, int sg_log2h) {
+    const int ng = 64 / sg;
+    const size_t small = hash ? (size_t)ng * LEI_SG_AREA_OF(sg_log2h) * sizeof(int) : (size_t)ng * lei_wslots_bytes(LEI_SG_CAP, LEI_SG_LOG2H - 1);
+    // table (3 ints per entry) + occupied-entry list: a counter (16 B) and one 16-bit slot per edge
+    const size_t big = hash ? (size_t)3 * ((size_t)1 << big_log2h) * sizeof(int) + 16 + (((size_t)lds_cap * 2 + 15) & ~(size_t)15)
+                            : lei_wslots_bytes(lds_cap, big_log2h);
+    return small > big ? small : big;
 }
 
 // evaluation of the nodes [a.b0, a.b1) (+ the wide nodes a.big0..a.big1 of that range) against the frozen state
@@ -1188,6 +556,23 @@ static int lei_sub_group(const mn_graph *g, int use_both) {
     if (const char *e = getenv("MN_LEIDEN_SG")) // tuning knob: 16 or 32 lanes per node
         sg = atoi(e) == 16 ? 16 : 32;
     return sg;
+}
+
+// Weighted graph, the decisions of the nb nodes [a.b0, a.b1) are in: several winners may share a community and f64 addition
+// is not associative → the operations are grouped by community with a stable sort and every community replays its own in
+// node order.  sum_tot is then up to date; the apply kernel that follows moves the labels.
+static int lei_apply_weighted(mn_graph *g, const LeiArgs &a, int nb, hipStream_t st) {
+    LeiWork &w = *g->work;
+    const int n_ops = 2 * nb;
+    hipLaunchKernelGGL(k_leiden_ops, dim3((nb + 255) / 256), dim3(256), 0, st, a, g->n, w.okeys);
+    size_t bytes = w.osort_bytes;
+    if (rocprim::radix_sort_pairs(w.osort_tmp.p, bytes, w.okeys.p, w.okeys_s.p, w.oiota.p, w.oops_s.p, (size_t)n_ops, 0, w.osort_bits, st) !=
+        hipSuccess) {
+        gset_err("rocprim::radix_sort_pairs failed");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_leiden_apply_ops, dim3((n_ops + 255) / 256), dim3(256), 0, st, a, g->n, w.okeys_s, w.oops_s, n_ops);
+    return 0;
 }
 
 // one phase (local moving when elig_part == nullptr, refinement otherwise); returns moves, -1 on error
@@ -1244,20 +629,8 @@ static long long run_phase(mn_graph *g, LeiArgs a, int mode, int batch, int64_t 
             a.big1 = (int)bigpos;
             lei_launch_eval(a, nb, sg, hashed, st);
             hipLaunchKernelGGL(k_leiden_win, dim3((nb * 8 + 255) / 256), dim3(256), 0, st, a);
-            if (!a.apply_on_device) {
-                // weighted graph: several winners may share a community and f64 addition is not associative → the round's
-                // operations are grouped by community with a stable sort and every community replays its own in node order
-                LeiWork &w = *g->work;
-                const int n_ops = 2 * nb;
-                hipLaunchKernelGGL(k_leiden_ops, dim3((nb + 255) / 256), dim3(256), 0, st, a, g->n, w.okeys);
-                size_t bytes = w.osort_bytes;
-                if (rocprim::radix_sort_pairs(w.osort_tmp, bytes, w.okeys, w.okeys_s, w.oiota, w.oops_s, (size_t)n_ops, 0, w.osort_bits,
-                                              st) != hipSuccess) {
-                    gset_err("rocprim::radix_sort_pairs failed");
-                    return -1;
-                }
-                hipLaunchKernelGGL(k_leiden_apply_ops, dim3((n_ops + 255) / 256), dim3(256), 0, st, a, g->n, w.okeys_s, w.oops_s, n_ops);
-            }
+            if (!a.apply_on_device && lei_apply_weighted(g, a, nb, st))
+                return -1;
             hipLaunchKernelGGL(k_leiden_apply, dim3((nb + 255) / 256), dim3(256), 0, st, a); // resets tallies (+ applies)
             parity ^= 1;
         }
@@ -1294,6 +667,15 @@ static long long run_phase(mn_graph *g, LeiArgs a, int mode, int batch, int64_t 
     return total;
 }
 
+// A rank's share of the nodes, [v0, v1): `per` nodes a rank, the last ranks' short or empty; no communicator = one rank
+struct LeiRange {
+    int world, rank, per, v0, v1;
+};
+static LeiRange lei_rank_range(const mn_comm *c, int N) {
+    const int world = c ? c->world : 1, rank = c ? c->rank : 0, per = (N + world - 1) / world, v0 = std::min(N, rank * per);
+    return {world, rank, per, v0, std::min(N, v0 + per)};
+}
+
 // Default schedule of MN_LEIDEN_BATCHED since round 4: WHOLE-GRAPH synchronous sweeps (oracle/mn_graph_oracle.c sync_phase is
 // the restatement, bit for bit).  A sweep = k_leiden_eval over every node against the state frozen at its start +
 // k_leiden_apply_sync applying EVERY positive-gain mover (weighted graphs: sum_tot in node order through the stable sort of
@@ -1308,7 +690,7 @@ static int lei_round_default(int N) { return (int)std::min<long long>(16384, std
 static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, int64_t *sweeps_out) {
     hipStream_t st = g->stream;
     LeiWork &w = *g->work;
-    const int N = g->n, nbN = (N + 255) / 256;
+    const int N = g->n;
     const bool hashed = !g->weighted;
     const int sg = lei_sub_group(g, a.use_both);
     int cap = LEI_SYNC_CAP;
@@ -1317,11 +699,9 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
     // Several GPUs (mn_graph_leiden_shared): every rank holds the graph and the whole state; the evaluation — four fifths of a
     // sweep — is divided by node range, the decisions are all-gathered (N ints per sweep) and every replica applies ALL of them,
     // so every rank walks through the same states as one GPU does and ends with its bits.
-    const int world = c ? c->world : 1, rank = c ? c->rank : 0;
-    const int per = (N + world - 1) / world;
-    const int v0 = std::min(N, rank * per), v1 = std::min(N, v0 + per);
-    const int bg0 = (int)(std::lower_bound(w.h_big.begin(), w.h_big.end(), v0) - w.h_big.begin());
-    const int bg1 = (int)(std::lower_bound(w.h_big.begin(), w.h_big.end(), v1) - w.h_big.begin());
+    const LeiRange r = lei_rank_range(c, N);
+    const int bg0 = (int)(std::lower_bound(w.h_big.begin(), w.h_big.end(), r.v0) - w.h_big.begin());
+    const int bg1 = (int)(std::lower_bound(w.h_big.begin(), w.h_big.end(), r.v1) - w.h_big.begin());
     int *const dec_all = a.dec;
     a.sync = 1;
     a.parity = 0;
@@ -1334,14 +714,14 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
         // (table size is a matter of speed only: full-size while most neighbours still carry labels of their own)
         a.sg_log2h = sweeps <= 3 || getenv("MN_LEIDEN_FULL_TABLES") ? LEI_SG_LOG2H : LEI_SG_LOG2H - 1;
         GCHK(hipMemsetAsync(a.out, 0, sizeof(int), st));
-        a.b0 = v0;
-        a.b1 = v1;
+        a.b0 = r.v0;
+        a.b1 = r.v1;
         a.big0 = bg0;
         a.big1 = bg1;
-        a.dec = dec_all + v0; // (the evaluation stores decision v at dec[v - b0])
-        if (v1 > v0)
-            lei_launch_eval(a, v1 - v0, sg, hashed, st);
-        if (world > 1) {
+        a.dec = dec_all + r.v0; // (the evaluation stores decision v at dec[v - b0])
+        if (r.v1 > r.v0)
+            lei_launch_eval(a, r.v1 - r.v0, sg, hashed, st);
+        if (r.world > 1) {
             int failed = -1;
             const int ag = mn_comm_agree(c, hipGetLastError() != hipSuccess ? 1 : 0, st, &failed);
             if (ag != 0) {
@@ -1351,7 +731,7 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
                     gset_err("mn_graph_leiden_shared: rank %d failed; all ranks stop", failed);
                 return -1;
             }
-            if (mn_comm_allgather_dev(c, dec_all + (size_t)rank * per, dec_all, (size_t)per * sizeof(int), st)) {
+            if (mn_comm_allgather_dev(c, dec_all + (size_t)r.rank * r.per, dec_all, (size_t)r.per * sizeof(int), st)) {
                 gset_err("mn_graph_leiden_shared: %s", mn_comm_last_error_str());
                 return -1;
             }
@@ -1359,18 +739,9 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
         a.b0 = 0;
         a.b1 = N;
         a.dec = dec_all;
-        if (!a.apply_on_device) {
-            const int n_ops = 2 * N;
-            hipLaunchKernelGGL(k_leiden_ops, dim3(nbN), dim3(256), 0, st, a, N, w.okeys);
-            size_t bytes = w.osort_bytes;
-            if (rocprim::radix_sort_pairs(w.osort_tmp, bytes, w.okeys, w.okeys_s, w.oiota, w.oops_s, (size_t)n_ops, 0, w.osort_bits, st) !=
-                hipSuccess) {
-                gset_err("rocprim::radix_sort_pairs failed");
-                return -1;
-            }
-            hipLaunchKernelGGL(k_leiden_apply_ops, dim3((n_ops + 255) / 256), dim3(256), 0, st, a, N, w.okeys_s, w.oops_s, n_ops);
-        }
-        hipLaunchKernelGGL(k_leiden_apply_sync, dim3(nbN), dim3(256), 0, st, a);
+        if (!a.apply_on_device && lei_apply_weighted(g, a, N, st))
+            return -1;
+        hipLaunchKernelGGL(k_leiden_apply_sync, dim3((N + 255) / 256), dim3(256), 0, st, a);
         GCHK(hipGetLastError());
         GCHK(hipMemcpyAsync(w.h_out, a.out, sizeof(int), hipMemcpyDeviceToHost, st));
         GCHK(hipStreamSynchronize(st));
@@ -1381,13 +752,8 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
             break;
         }
     }
-    a.b0 = 0;
-    a.b1 = N;
-    a.big0 = 0;
-    a.big1 = (int)w.h_big.size();
-    a.dec = dec_all;
     *sweeps_out += sweeps;
-    if (!converged) {
+    if (!converged) { // the round schedule finishes the phase (a.dec is dec_all again; run_phase sets every round's range)
         a.sync = 0;
         a.pickless = 0;
         a.sg_log2h = LEI_SG_LOG2H;
@@ -1399,230 +765,291 @@ static long long run_phase_sync(mn_graph *g, mn_comm *c, LeiArgs a, int period, 
     return total;
 }
 
+// ───────────────────────── bookkeeping between the phases ─────────────────────────
+// The three places where run_leiden touches every node outside a phase, written twice and chosen once per call (LeiBook).
+// On the device for unweighted graphs under the parallel schedules: every sum is then a sum of integers below 2^53, exact in
+// any order, so atomics give the reference's bits; first-seen renumbering = atomicMin of the first index per label + a prefix
+// sum over the first-occurrence flags.  On the host otherwise: f64 addition is not associative, the sums are taken in the
+// reference's node order.  The device holds k[i] in kdeg when begin runs, the singletons in label / sum_tot after it
+// (leiden_impl), the renumbered partition and its sums after after_refinement.
+
+struct LeiRun { // one call, as its bookkeeping sees it
+    mn_graph *g;
+    mn_comm *c;
+    LeiWork &d;
+    DevGraph dg;
+    hipStream_t st;
+    int N, nbN, use_both;
+    double m = 0.0;                  // :344-350
+    int K = 0;                       // finish: communities, and their s_in / s_tot of compute_modularity (:128-139)
+    std::vector<double> s_in, s_tot;
+    std::vector<double> k, sum_tot;  // host bookkeeping: k[i], sum_tot[c] ...
+    std::vector<int> community, refined; // ... and the two partitions
+};
+struct LeiBook {
+    int (*begin)(LeiRun &r);            // m, not yet halved (:344-349); the host's copy of k[i]
+    int (*after_refinement)(LeiRun &r); // adopt `refined` iff not more communities (:385-408), renumber, rebuild sum_tot (:410-416)
+    int (*finish)(LeiRun &r, int *community_out); // renumber (:420); K, s_in, s_tot (:109-127); ends the timed span (ev1)
+};
+
 // compute_modularity's per-node terms weight_to_community(i, community[i]) (:131): each rank computes those of its node range
 // and the ranges are all-gathered — the modularity partials of several GPUs.  (Gathered per NODE rather than reduced per
 // community: the per-community f64 sums are then taken in the reference's node order on every rank, the same bits as one GPU.)
-static int lei_w2c_all(mn_graph *g, mn_comm *c, const DevGraph &dg, int use_both, const int *label, double *tmp) {
-    hipStream_t st = g->stream;
-    const int N = g->n, world = c ? c->world : 1, rank = c ? c->rank : 0;
-    const int per = (N + world - 1) / world;
-    const int v0 = std::min(N, rank * per), v1 = std::min(N, v0 + per);
-    if (v1 > v0)
-        hipLaunchKernelGGL(k_w2c_self, dim3((v1 - v0 + 255) / 256), dim3(256), 0, st, dg, use_both, label, tmp, v0, v1);
-    if (world > 1 && mn_comm_allgather_dev(c, tmp + (size_t)rank * per, tmp, (size_t)per * sizeof(double), st)) {
+static int lei_w2c_all(const LeiRun &run, const int *label, double *tmp) {
+    const LeiRange r = lei_rank_range(run.c, run.N);
+    if (r.v1 > r.v0)
+        hipLaunchKernelGGL(k_w2c_self, dim3((r.v1 - r.v0 + 255) / 256), dim3(256), 0, run.st, run.dg, run.use_both, label, tmp, r.v0, r.v1);
+    if (r.world > 1 && mn_comm_allgather_dev(run.c, tmp + (size_t)r.rank * r.per, tmp, (size_t)r.per * sizeof(double), run.st)) {
         gset_err("mn_graph_leiden_shared: %s", mn_comm_last_error_str());
         return -1;
     }
     return 0;
 }
 
-static int leiden_impl(mn_graph *g, mn_comm *c, double resolution, int use_both, int mode, int batch, int *community_out,
-                       double *modularity_out) {
-    GCHK(hipSetDevice(g->device));
-    const int N = g->n;
-    memset(&g->stats, 0, sizeof(g->stats));
-    if (modularity_out)
-        *modularity_out = 0.0;
-    if (N == 0)
-        return 0;
-    // MN_LEIDEN_BATCHED: batch 0 / 1 = the default schedule, whole-graph synchronous sweeps with a pick-less sweep every
-    // LEI_PICKLESS (run_phase_sync); batch < 0 = the same with period -batch; batch > 1 = rounds of `batch` nodes with the
-    // safe-winner commit rule (run_phase) — also what finishes a synchronous phase that does not settle.
-    int period = 0;
-    if (mode == MN_LEIDEN_BATCHED && batch <= 1) {
-        period = batch < 0 ? -batch : LEI_PICKLESS;
-        if (const char *e = getenv("MN_LEIDEN_BATCH")) { // tuning knob: MN_LEIDEN_BATCH=<round size> selects the round schedule
-            if (atoi(e) > 1) {
-                period = 0;
-                batch = std::max(256, atoi(e));
-            }
-        }
-        if (period)
-            batch = lei_round_default(N); // the rounds a synchronous phase falls back to
+// distinct labels of `label` → counts[slot] (device), leaves first[] / flag[] describing `label`
+static int dev_distinct(LeiRun &r, const int *label, int slot) {
+    GCHK(hipMemsetAsync(r.d.first, 0x7f, (size_t)r.N * sizeof(int), r.st));
+    GCHK(hipMemsetAsync(r.d.counts + slot, 0, sizeof(int), r.st));
+    hipLaunchKernelGGL(k_first_seen, dim3(r.nbN), dim3(256), 0, r.st, label, r.N, r.d.first);
+    hipLaunchKernelGGL(k_first_flag, dim3(r.nbN), dim3(256), 0, r.st, label, r.d.first, r.N, r.d.flag, r.d.counts + slot);
+    return 0;
+}
+// renumber `label` in place in first-seen order (first[] / flag[] must describe it: dev_distinct)
+static int dev_renumber(LeiRun &r, int *label) {
+    size_t bytes = r.d.scan_bytes;
+    if (rocprim::exclusive_scan(r.d.scan_tmp.p, bytes, r.d.flag.p, r.d.rank.p, 0, (size_t)r.N, rocprim::plus<int>(), r.st) != hipSuccess) {
+        gset_err("rocprim::exclusive_scan failed");
+        return -1;
     }
-    hipStream_t st = g->stream;
-    DevGraph dg = {N, g->off_out, g->tgt_out, g->w_out, g->off_in, g->tgt_in, g->w_in};
-    const int max_deg = ((use_both ? g->max_deg_both : g->max_deg_out) + 7) & ~3; // int4-aligned scratch stride
-    // buffers hold the largest round of the schedule (run_phase's tail rule)
+    hipLaunchKernelGGL(k_relabel, dim3(r.nbN), dim3(256), 0, r.st, label, r.d.first, r.d.rank, r.N);
+    return 0;
+}
+static int dev_begin(LeiRun &r) {
+    GCHK(hipMemsetAsync(r.d.scal, 0, sizeof(double), r.st));
+    hipLaunchKernelGGL(k_sum_d, dim3(std::min(r.nbN, 1024)), dim3(256), 0, r.st, r.d.kdeg, r.N, r.d.scal);
+    GCHK(hipMemcpyAsync(&r.m, r.d.scal, sizeof(double), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    return 0;
+}
+static int dev_after_refinement(LeiRun &r) {
+    LeiWork &d = r.d;
+    int cnt[2] = {0, 0};
+    if (dev_distinct(r, d.label, 0) || dev_distinct(r, d.refined, 1))
+        return -1;
+    GCHK(hipMemcpyAsync(cnt, d.counts, sizeof(cnt), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    if (cnt[1] <= cnt[0]) { // first[] / flag[] describe `refined` (the later of the two calls)
+        GCHK(hipMemcpyAsync(d.label, d.refined, (size_t)r.N * sizeof(int), hipMemcpyDeviceToDevice, r.st));
+    } else if (dev_distinct(r, d.label, 0)) {
+        return -1;
+    }
+    if (dev_renumber(r, d.label))
+        return -1;
+    GCHK(hipMemsetAsync(d.sum_tot, 0, (size_t)r.N * sizeof(double), r.st));
+    hipLaunchKernelGGL(k_scatter_add, dim3(r.nbN), dim3(256), 0, r.st, d.label, d.kdeg, r.N, d.sum_tot);
+    return 0;
+}
+static int dev_finish(LeiRun &r, int *community_out) {
+    LeiWork &d = r.d;
+    const size_t n = (size_t)r.N;
+    if (dev_distinct(r, d.label, 0) || dev_renumber(r, d.label) || lei_w2c_all(r, d.label, d.tmp))
+        return -1;
+    GCHK(hipMemsetAsync(d.s_in, 0, n * sizeof(double), r.st));
+    GCHK(hipMemsetAsync(d.sum_tot, 0, n * sizeof(double), r.st));
+    hipLaunchKernelGGL(k_scatter_add, dim3(r.nbN), dim3(256), 0, r.st, d.label, d.tmp, r.N, d.s_in);
+    hipLaunchKernelGGL(k_scatter_add, dim3(r.nbN), dim3(256), 0, r.st, d.label, d.kdeg, r.N, d.sum_tot);
+    GCHK(hipMemcpyAsync(&r.K, d.counts, sizeof(int), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipMemcpyAsync(community_out, d.label, n * sizeof(int), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    r.s_in.resize((size_t)r.K);
+    r.s_tot.resize((size_t)r.K);
+    GCHK(hipMemcpyAsync(r.s_in.data(), d.s_in, (size_t)r.K * sizeof(double), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipMemcpyAsync(r.s_tot.data(), d.sum_tot, (size_t)r.K * sizeof(double), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipEventRecord(r.g->ev1, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    return 0;
+}
+
+static int renumber(std::vector<int> &c) { // :317-331
+    const int N = (int)c.size();
+    std::vector<int> map((size_t)N, -1);
+    int next = 0;
+    for (int i = 0; i < N; i++) {
+        if (map[c[i]] == -1)
+            map[c[i]] = next++;
+        c[i] = map[c[i]];
+    }
+    return next;
+}
+static int host_begin(LeiRun &r) {
+    r.k.resize((size_t)r.N);
+    GCHK(hipMemcpyAsync(r.k.data(), r.d.kdeg, (size_t)r.N * sizeof(double), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    for (int i = 0; i < r.N; i++) // the running total in node order
+        r.m += r.k[i];
+    r.community.resize((size_t)r.N); // (both partitions are read back from the device when they are needed)
+    r.refined.resize((size_t)r.N);
+    r.sum_tot = r.k;
+    return 0;
+}
+static int host_after_refinement(LeiRun &r) {
+    const size_t n = (size_t)r.N;
+    GCHK(hipMemcpyAsync(r.community.data(), r.d.label, n * sizeof(int), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipMemcpyAsync(r.refined.data(), r.d.refined, n * sizeof(int), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    if (renumber(r.refined) <= renumber(r.community)) // (the one that stays is renumbered anyway; renumbering counts the labels)
+        r.community = r.refined;
+    std::fill(r.sum_tot.begin(), r.sum_tot.end(), 0.0); // node order
+    for (int i = 0; i < r.N; i++)
+        r.sum_tot[r.community[i]] += r.k[i];
+    GCHK(hipMemcpyAsync(r.d.label, r.community.data(), n * sizeof(int), hipMemcpyHostToDevice, r.st));
+    GCHK(hipMemcpyAsync(r.d.sum_tot, r.sum_tot.data(), n * sizeof(double), hipMemcpyHostToDevice, r.st));
+    return 0;
+}
+static int host_finish(LeiRun &r, int *community_out) {
+    const size_t n = (size_t)r.N;
+    GCHK(hipMemcpyAsync(r.community.data(), r.d.label, n * sizeof(int), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    r.K = renumber(r.community);
+    // per-node terms on the device, accumulation in node order here
+    GCHK(hipMemcpyAsync(r.d.label, r.community.data(), n * sizeof(int), hipMemcpyHostToDevice, r.st));
+    if (lei_w2c_all(r, r.d.label, r.d.tmp))
+        return -1;
+    std::vector<double> w2c(n);
+    GCHK(hipMemcpyAsync(w2c.data(), r.d.tmp, n * sizeof(double), hipMemcpyDeviceToHost, r.st));
+    GCHK(hipEventRecord(r.g->ev1, r.st));
+    GCHK(hipStreamSynchronize(r.st));
+    r.s_in.assign((size_t)r.K, 0.0);
+    r.s_tot.assign((size_t)r.K, 0.0);
+    for (int i = 0; i < r.N; i++) {
+        r.s_tot[r.community[i]] += r.k[i];
+        r.s_in[r.community[i]] += w2c[i];
+    }
+    memcpy(community_out, r.community.data(), n * sizeof(int));
+    return 0;
+}
+static const LeiBook lei_book_dev = {dev_begin, dev_after_refinement, dev_finish};
+static const LeiBook lei_book_host = {host_begin, host_after_refinement, host_finish};
+
+// ───────────────────────── run_leiden (:336-429) ─────────────────────────
+// MN_LEIDEN_BATCHED: batch 0 / 1 = the default schedule, whole-graph synchronous sweeps with a pick-less sweep every
+// LEI_PICKLESS (run_phase_sync, period > 0); batch < 0 = the same with period -batch; batch > 1 = rounds of `batch` nodes with
+// the safe-winner commit rule (run_phase) — also what finishes a synchronous phase that does not settle.  round_cap: what the
+// per-round buffers hold — the largest round of the schedule (run_phase's tail rule), a whole sweep's decisions if period.
+struct LeiSchedule {
+    int period, batch, round_cap;
+};
+static LeiSchedule lei_schedule(int mode, int batch, int N) {
+    LeiSchedule s = {0, batch, batch};
+    if (mode != MN_LEIDEN_BATCHED)
+        return s;
+    if (batch <= 1) {
+        s.period = batch < 0 ? -batch : LEI_PICKLESS;
+        const char *e = getenv("MN_LEIDEN_BATCH"); // tuning knob: MN_LEIDEN_BATCH=<round size> selects the round schedule
+        if (e && atoi(e) > 1) {
+            s.period = 0;
+            s.batch = std::max(256, atoi(e));
+        }
+        if (s.period)
+            s.batch = lei_round_default(N); // the rounds a synchronous phase falls back to
+    }
     int grow_cap, div_unused;
     lei_grow_setting(&grow_cap, &div_unused);
-    const int round_cap = (int)std::min<long long>((long long)batch * grow_cap, std::max(batch, N));
-    if (lei_prepare(g, mode, mode == MN_LEIDEN_BATCHED ? (period ? std::max(round_cap, N) : round_cap) : batch, use_both, max_deg))
-        return -1;
-    LeiWork &d = *g->work;
-    const int nbN = (N + 255) / 256;
-    // Unweighted: every per-community / per-graph sum is a sum of integers (exact in any order) → all bookkeeping on the
-    // device.  Weighted: the reference's node-order f64 sums are kept on the host.
-    const bool on_dev = !g->weighted && mode == MN_LEIDEN_BATCHED;
-    GCHK(hipEventRecord(g->ev0, st));
-    // k[i], m (:344-350)
-    hipLaunchKernelGGL(k_wdeg, dim3(nbN), dim3(256), 0, st, dg, use_both, d.kdeg);
-    std::vector<double> k;
-    double m = 0.0;
-    if (on_dev) {
-        GCHK(hipMemsetAsync(d.scal, 0, sizeof(double), st));
-        hipLaunchKernelGGL(k_sum_d, dim3(std::min(nbN, 1024)), dim3(256), 0, st, d.kdeg, N, d.scal);
-        GCHK(hipMemcpyAsync(&m, d.scal, sizeof(double), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-    } else {
-        k.resize((size_t)N);
-        GCHK(hipMemcpyAsync(k.data(), d.kdeg, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < N; i++) // the running total in node order
-            m += k[i];
-    }
-    m /= 2.0;
-    std::vector<int> community, refined;
-    if (m <= 0.0) { // :351-356
-        for (int i = 0; i < N; i++)
-            community_out[i] = i;
-        return 0;
-    }
-    hipLaunchKernelGGL(k_iota, dim3(nbN), dim3(256), 0, st, d.label, N);
-    GCHK(hipMemcpyAsync(d.sum_tot, d.kdeg, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
-    std::vector<double> sum_tot;
-    if (!on_dev) {
-        community.resize((size_t)N);
-        refined.resize((size_t)N);
-        for (int i = 0; i < N; i++)
-            community[i] = i;
-        sum_tot = k;
-    }
+    s.round_cap = (int)std::min<long long>((long long)s.batch * grow_cap, std::max(s.batch, N));
+    if (s.period)
+        s.round_cap = std::max(s.round_cap, N);
+    return s;
+}
 
+// the kernels' arguments that hold for the whole run (a phase sets label / sum_tot / elig_part, a round its range)
+static LeiArgs lei_args(const LeiRun &r, double resolution, int max_deg) {
+    const LeiWork &d = r.d;
     LeiArgs a;
     memset(&a, 0, sizeof(a));
-    a.g = dg;
+    a.g = r.dg;
     a.kdeg = d.kdeg;
-    a.m = m;
+    a.m = r.m;
     a.resolution = resolution;
-    a.use_both = use_both;
-    a.scratch_c = d.sc;
-    a.scratch_w = d.sw;
-    a.scratch_e = d.se;
+    a.use_both = r.use_both;
+    a.scratch_c = d.sc, a.scratch_w = d.sw, a.scratch_e = d.se;
     a.max_deg = max_deg;
     a.out = d.out;
     a.max_sweeps = 100000;
-    a.dec = d.dec;
-    a.cmin = d.cmin;
-    a.win = d.win;
-    a.mv = d.mv;
-    a.dk = d.dk;
-    a.Jq = d.Jq;
-    a.Lq = d.Lq;
-    a.apply_on_device = g->weighted ? 0 : 1;
+    a.dec = d.dec, a.dk = d.dk, a.win = d.win, a.mv = d.mv; // a round's
+    a.cmin = d.cmin, a.Jq = d.Jq, a.Lq = d.Lq;              // per community
+    a.apply_on_device = r.g->weighted ? 0 : 1;
     a.lds_cap = std::min(LEI_CAP, std::max(64, (max_deg + 15) & ~15));
     a.big_log2h = 8; // a wide node's table: one entry per edge at most (only other communities enter it)
     while ((1 << a.big_log2h) < a.lds_cap)
         a.big_log2h++;
     a.sg_log2h = LEI_SG_LOG2H;
-    a.biglist = d.biglist;
-    a.bigoff = d.bigoff;
+    a.biglist = d.biglist, a.bigoff = d.bigoff;
+    return a;
+}
 
+static int leiden_impl(mn_graph *g, mn_comm *c, double resolution, int use_both, int mode, int batch, int *community_out,
+                       double *modularity_out) {
+    GCHK(hipSetDevice(g->device));
+    const int N = g->n, nbN = (N + 255) / 256;
+    memset(&g->stats, 0, sizeof(g->stats));
+    if (modularity_out)
+        *modularity_out = 0.0;
+    if (N == 0) // :338-339
+        return 0;
+    const LeiSchedule s = lei_schedule(mode, batch, N);
+    const int max_deg = ((use_both ? g->max_deg_both : g->max_deg_out) + 7) & ~3; // int4-aligned scratch stride
+    if (lei_prepare(g, mode, s.round_cap, use_both, max_deg))
+        return -1;
+    hipStream_t st = g->stream;
+    LeiWork &d = *g->work;
+    LeiRun r = {g, c, d, dev_graph_of(g), st, N, nbN, use_both};
+    const LeiBook &book = !g->weighted && mode == MN_LEIDEN_BATCHED ? lei_book_dev : lei_book_host;
+    GCHK(hipEventRecord(g->ev0, st));
+    hipLaunchKernelGGL(k_wdeg, dim3(nbN), dim3(256), 0, st, r.dg, use_both, d.kdeg); // k[i], m (:344-350)
+    if (book.begin(r))
+        return -1;
+    r.m /= 2.0;
+    if (r.m <= 0.0) { // :351-356
+        for (int i = 0; i < N; i++)
+            community_out[i] = i;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_iota, dim3(nbN), dim3(256), 0, st, d.label, N); // :358-365
+    GCHK(hipMemcpyAsync(d.sum_tot, d.kdeg, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    LeiArgs a = lei_args(r, resolution, max_deg);
+    const auto phase = [&](int64_t *sweeps) {
+        return s.period ? run_phase_sync(g, c, a, s.period, sweeps) : run_phase(g, a, mode, s.batch, sweeps);
+    };
     for (int iter = 0; iter < 100; iter++) { // :368-417
-        a.label = d.label;
+        a.label = d.label; // local moving (:372)
         a.sum_tot = d.sum_tot;
         a.elig_part = nullptr;
-        long long moves = period ? run_phase_sync(g, c, a, period, &g->stats.move_sweeps) : run_phase(g, a, mode, batch, &g->stats.move_sweeps);
+        const long long moves = phase(&g->stats.move_sweeps);
         if (moves < 0)
             return -1;
         g->stats.iterations++;
         g->stats.moves += moves;
         if (moves == 0)
             break;
-        // refinement (:238-312): singletons, r_sum_tot = k
+        // refinement (:383, :238-312): singletons, r_sum_tot = k, moves inside the phase-1 communities only
         hipLaunchKernelGGL(k_iota, dim3(nbN), dim3(256), 0, st, d.refined, N);
         GCHK(hipMemcpyAsync(d.tmp, d.kdeg, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
         a.label = d.refined;
         a.sum_tot = d.tmp;
         a.elig_part = d.label;
-        if (!on_dev) {
-            GCHK(hipMemcpyAsync(community.data(), d.label, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
-            for (int i = 0; i < N; i++)
-                refined[i] = i;
-        }
-        if ((period ? run_phase_sync(g, c, a, period, &g->stats.refine_sweeps) : run_phase(g, a, mode, batch, &g->stats.refine_sweeps)) < 0)
+        if (phase(&g->stats.refine_sweeps) < 0 || book.after_refinement(r)) // :385-416
             return -1;
-        if (on_dev) {
-            // :388-408 adopt the refinement iff it has no more communities than phase 1; then renumber (:317-331)
-            // and rebuild sum_tot (:413-416) — on the device
-            int cnt[2] = {0, 0};
-            if (dev_distinct(g, d.label, 0) || dev_distinct(g, d.refined, 1))
-                return -1;
-            GCHK(hipMemcpyAsync(cnt, d.counts, sizeof(cnt), hipMemcpyDeviceToHost, st));
-            GCHK(hipStreamSynchronize(st));
-            if (cnt[1] <= cnt[0]) { // first[] / flag[] describe `refined` (the later of the two calls)
-                GCHK(hipMemcpyAsync(d.label, d.refined, (size_t)N * sizeof(int), hipMemcpyDeviceToDevice, st));
-            } else if (dev_distinct(g, d.label, 0)) {
-                return -1;
-            }
-            if (dev_renumber(g, d.label))
-                return -1;
-            GCHK(hipMemsetAsync(d.sum_tot, 0, (size_t)N * sizeof(double), st));
-            hipLaunchKernelGGL(k_scatter_add, dim3(nbN), dim3(256), 0, st, d.label, d.kdeg, N, d.sum_tot);
-        } else {
-            GCHK(hipMemcpyAsync(refined.data(), d.refined, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
-            GCHK(hipStreamSynchronize(st));
-            if (distinct(refined) <= distinct(community)) // :388-408
-                community = refined;
-            renumber(community);
-            std::fill(sum_tot.begin(), sum_tot.end(), 0.0); // :413-416, node order
-            for (int i = 0; i < N; i++)
-                sum_tot[community[i]] += k[i];
-            GCHK(hipMemcpyAsync(d.label, community.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, st));
-            GCHK(hipMemcpyAsync(d.sum_tot, sum_tot.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
-        }
     }
-    int K = 0;
-    std::vector<double> s_in, s_tot;
-    if (on_dev) {
-        int cnt = 0;
-        if (dev_distinct(g, d.label, 0) || dev_renumber(g, d.label)) // :420
-            return -1;
-        // compute_modularity (:109-142): per-node terms and per-community sums (integers) on the device
-        if (lei_w2c_all(g, c, dg, use_both, d.label, d.tmp))
-            return -1;
-        GCHK(hipMemsetAsync(d.s_in, 0, (size_t)N * sizeof(double), st));
-        GCHK(hipMemsetAsync(d.sum_tot, 0, (size_t)N * sizeof(double), st));
-        hipLaunchKernelGGL(k_scatter_add, dim3(nbN), dim3(256), 0, st, d.label, d.tmp, N, d.s_in);
-        hipLaunchKernelGGL(k_scatter_add, dim3(nbN), dim3(256), 0, st, d.label, d.kdeg, N, d.sum_tot);
-        GCHK(hipMemcpyAsync(&cnt, d.counts, sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(community_out, d.label, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        K = cnt;
-        s_in.resize((size_t)K);
-        s_tot.resize((size_t)K);
-        GCHK(hipMemcpyAsync(s_in.data(), d.s_in, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(s_tot.data(), d.sum_tot, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-        GCHK(hipEventRecord(g->ev1, st));
-        GCHK(hipStreamSynchronize(st));
-    } else {
-        GCHK(hipMemcpyAsync(community.data(), d.label, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        K = renumber(community); // :420
-        // compute_modularity (:109-142): per-node terms on the device, accumulation in node order here
-        GCHK(hipMemcpyAsync(d.label, community.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, st));
-        if (lei_w2c_all(g, c, dg, use_both, d.label, d.tmp))
-            return -1;
-        std::vector<double> w2c((size_t)N);
-        GCHK(hipMemcpyAsync(w2c.data(), d.tmp, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-        GCHK(hipEventRecord(g->ev1, st));
-        GCHK(hipStreamSynchronize(st));
-        s_in.assign((size_t)K, 0.0);
-        s_tot.assign((size_t)K, 0.0);
-        for (int i = 0; i < N; i++) {
-            s_tot[community[i]] += k[i];
-            s_in[community[i]] += w2c[i];
-        }
-        memcpy(community_out, community.data(), (size_t)N * sizeof(int));
-    }
+    if (book.finish(r, community_out)) // :420, and compute_modularity's sums (:109-127)
+        return -1;
     double Q = 0.0; // :128-139, communities in order (K terms)
-    for (int c = 0; c < K; c++)
-        if (s_tot[c] > 0)
-            Q += s_in[c] / (2.0 * m) - resolution * (s_tot[c] / (2.0 * m)) * (s_tot[c] / (2.0 * m));
+    for (int q = 0; q < r.K; q++)
+        if (r.s_tot[q] > 0)
+            Q += r.s_in[q] / (2.0 * r.m) - resolution * (r.s_tot[q] / (2.0 * r.m)) * (r.s_tot[q] / (2.0 * r.m));
     float ms = 0;
     if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
         g->stats.device_ms = ms;
-    g->stats.n_communities = K;
+    g->stats.n_communities = r.K;
     if (modularity_out)
         *modularity_out = Q;
     return 0;

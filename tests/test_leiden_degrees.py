@@ -1,4 +1,4 @@
-"""k_leiden_eval (csrc/mn_leiden.hip) picks its code per node by the node's degree (out + in), per graph by the largest and the
+"""k_leiden_eval (csrc/mn_leiden.hip, over csrc/mn_leiden_eval.hpp) picks its code per node by the node's degree (out + in), per graph by the largest and the
 mean degree, and per sweep by the sweep number.  The switches, as the source has them:
 
   degree <= LEI_SG_CAP (64)      a sub-group of 16 / 32 lanes evaluates the node; above: one wavefront per "wide" node (biglist)
@@ -29,7 +29,7 @@ import pytest
 from oracle import orc_graph as og
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "sqlite-muninn_amd", "csrc", "mn_leiden.hip")
+SRCS = [os.path.join(ROOT, "sqlite-muninn_amd", "csrc", f) for f in ("mn_leiden_eval.hpp", "mn_leiden.hip")]  # read as one text
 
 # the constants this table was written for (parsed out of the source and compared in the table test)
 CONSTANTS = {"LEI_SG_CAP": 64, "LEI_CAP": 1024, "LEI_WPB": 4, "LEI_SYNC_CAP": 48, "LEI_PICKLESS": 3, "LEI_GROW": 4,
@@ -314,7 +314,7 @@ def qbits(q):
 # ───────────────────────── 0. the table, on the CPU ─────────────────────────
 
 def test_source_constants_are_the_ones_the_table_was_written_for():
-    text = open(SRC).read()
+    text = "\n".join(open(p).read() for p in SRCS)
     for name, want in CONSTANTS.items():
         found = re.findall(rf"^#define\s+{name}\s+(\d+)\b", text, re.M)
         assert found == [str(want)], (name, found)
