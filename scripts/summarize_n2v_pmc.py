@@ -33,7 +33,7 @@ with open(os.path.join(ROOT, "profiles", f"{tag}_pmc_summary.csv"), "w") as out:
     out.write(f"kernel,dispatches_in_{batches}_batches,mean_FETCH_SIZE_KB,mean_WRITE_SIZE_KB,traffic_bytes_per_batch(2*FETCH+WRITE)\n")
     for r in rows:
         out.write('"%s",%d,%.3f,%.3f,%d\n' % r)
-srcs = ["mn_n2v.hip", "mn_n2v_batched.hpp"]
+srcs = ["mn_n2v.hip", "mn_n2v_dev.hpp", "mn_n2v_batched.hpp", "mn_n2v_shared.hpp"]
 tpath = os.path.join(ROOT, "profiles", "traffic.json")
 t = json.load(open(tpath))
 ent = t["node2vec_er1M_20M_batched_default"]

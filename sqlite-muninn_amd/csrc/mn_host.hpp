@@ -30,11 +30,12 @@ inline void mn_vformat(std::string &dst, const char *fmt, va_list ap) {
 struct DevArena {
     std::vector<void *> p;
     template <typename T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess)
+        p.push_back(nullptr); // the slot first: a growth that throws then leaves no buffer behind
+        if (hipMalloc(&p.back(), (n ? n : 1) * sizeof(T)) != hipSuccess) {
+            p.pop_back();
             return nullptr;
-        p.push_back(q);
-        return static_cast<T *>(q);
+        }
+        return static_cast<T *>(p.back());
     }
     ~DevArena() {
         for (void *q : p)

@@ -1,4 +1,4 @@
-// mn_n2v_batched.hpp — MN_N2V_BATCHED: the batch-synchronous Node2Vec schedule (included by mn_n2v.hip).
+// mn_n2v_batched.hpp — MN_N2V_BATCHED: the batch-synchronous Node2Vec schedule, its session and its two launchers.
 //
 // Per (epoch, w) pass the start nodes are cut into batches of B walks (DESIGN.md §node2vec;
 // oracle/mn_graph_oracle.c orc_node2vec_train_batched restates it):
@@ -17,10 +17,17 @@
 // centre-side update costs one row per walk position instead of (1+neg) rows per pair.
 // No float atomics anywhere: embeddings are bit-reproducible and equal the CPU restatement's.
 #pragma once
+#include "../../include/muninn_hip.h"
+#include "mn_host.hpp"
+#include "mn_n2v_dev.hpp"
+#include <algorithm>
 #include <cstring>
+#include <memory>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <type_traits>
 
-#define N2VB_LDS_DEG 512
+void nset_err(const char *fmt, ...); // the unit's thread-local error string (mn_n2v.hip)
+#define NCHK(expr) MN_HIPCHK(nset_err, expr)
 
 struct N2vBatchArgs {
     N2vArgs a;
@@ -43,6 +50,18 @@ DEVI unsigned n2v_walk_seed(int epoch, int w, int n) {
     s *= 0x2C1B3C6Du;
     s ^= s >> 12;
     return s ? s : 1u;
+}
+
+// A lane keeps elements lane + 64 r of a row in its register slots r; this writes them back.  The loads (`d < dim ? row[d] : 0`)
+// stay written out in the kernels: as a helper of this shape they compile to other code in k_n2v_apply and k_n2v_apply_centers
+// (profiles/refactor_n2v_ab.txt).
+template <int NR> DEVI void n2v_row_st(float *row, const float (&v)[NR], int dim, int lane) {
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        int d = lane + 64 * r;
+        if (d < dim)
+            row[d] = v[r];
+    }
 }
 
 // biased_walk (src/node2vec.c:168-226) for one wavefront; walk[] in LDS.  With p == q == 1 every weight is
@@ -75,49 +94,7 @@ DEVI int gen_walk(const N2vArgs &a, int n, unsigned &rng, int *walk, double *cum
                 i = deg - 1;
             chosen = a.adj[c0 + i];
         } else {
-            const bool in_lds = deg <= N2VB_LDS_DEG;
-            const int p0 = a.off[prev], degp = a.off[prev + 1] - p0;
-            __builtin_amdgcn_wave_barrier();
-            for (int i = lane; i < deg; i += 64) {
-                const int x = a.adj[c0 + i];
-                double wt;
-                if (x == prev) {
-                    wt = 1.0 / a.p;
-                } else {
-                    bool nb = false;
-                    for (int j = 0; j < degp; j++)
-                        if (a.adj[p0 + j] == x) {
-                            nb = true;
-                            break;
-                        }
-                    wt = nb ? 1.0 : 1.0 / a.q;
-                }
-                cum_st(cum_l, cum_g, in_lds, i, wt);
-            }
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) {
-                double t = 0.0;
-                for (int i = 0; i < deg; i++) {
-                    t += cum_ld(cum_l, cum_g, in_lds, i);
-                    cum_st(cum_l, cum_g, in_lds, i, t);
-                }
-            }
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_wave_barrier();
-            const double total = cum_ld(cum_l, cum_g, in_lds, deg - 1);
-            const double r = xs_rand(rng) * total;
-            int ci = 0x7fffffff;
-            for (int i = lane; i < deg; i += 64)
-                if (r <= cum_ld(cum_l, cum_g, in_lds, i)) {
-                    ci = i;
-                    break;
-                }
-            for (int m = 32; m >= 1; m >>= 1) {
-                int o = __shfl_xor(ci, m);
-                ci = o < ci ? o : ci;
-            }
-            chosen = ci == 0x7fffffff ? a.adj[c0] : a.adj[c0 + ci];
+            chosen = n2v_biased_pick<N2VB_LDS_DEG>(a, c0, deg, prev, cum_l, cum_g, lane, rng);
         }
         if (lane == 0)
             walk[step] = chosen;
@@ -248,13 +225,9 @@ __global__ void __launch_bounds__(64) k_n2v_walk_grad(N2vBatchArgs b) {
     for (int i = 0; i < pairs_p0 * a.neg; i++)
         xs32(rng);
     const int slot_end = part == b.split - 1 ? b.cap : pairs_pe * (1 + a.neg);
-#ifdef MN_N2V_PF // timing experiments only
-    constexpr int PF = MN_N2V_PF;
-#else
     // target rows in flight per wavefront.  Measured on MI355X (1M nodes, 20M edges, dim 128, neg 5: device time of one
     // pass of 1M walks, everything else equal): PF 2: 1.37 s, 3: 1.34 s, 6: 1.28 s (one branch-free chunk per pair)
     constexpr int PF = NR <= 4 ? 6 : 2;
-#endif
     int ns = pairs_p0 * (1 + a.neg);
     unsigned long long pairs = 0;
     for (int pos = p0; pos < pe; pos++) {
@@ -287,15 +260,8 @@ __global__ void __launch_bounds__(64) k_n2v_walk_grad(N2vBatchArgs b) {
         }
         if (lane == 0)
             b.p_center[pbase + pos] = center;
-#ifndef MN_N2V_NO_PNEU // timing experiments only
         float *pn = b.p_neu + (pbase + pos) * dim;
-#pragma unroll
-        for (int r = 0; r < NR; r++) {
-            int d = lane + 64 * r;
-            if (d < dim)
-                pn[d] = neu[r];
-        }
-#endif
+        n2v_row_st(pn, neu, dim, lane);
     }
     for (int i = ns + lane; i < slot_end; i += 64) {
         b.s_center[base + i] = -1;
@@ -394,12 +360,7 @@ __global__ void __launch_bounds__(64)
         j += 64;
     }
     float *out = dst_out + (size_t)k * dim;
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-        int d = lane + 64 * r;
-        if (d < dim)
-            out[d] = acc[r];
-    }
+    n2v_row_st(out, acc, dim, lane);
 }
 
 // centre row: staged = row + Σ neu1e of the walk positions centred on it, in (walk, position) order
@@ -429,12 +390,7 @@ __global__ void __launch_bounds__(64)
         }
     }
     float *out = dst_out + (size_t)k * dim;
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-        int d = lane + 64 * r;
-        if (d < dim)
-            out[d] = acc[r];
-    }
+    n2v_row_st(out, acc, dim, lane);
 }
 
 __global__ void __launch_bounds__(64)
@@ -447,42 +403,66 @@ __global__ void __launch_bounds__(64)
 }
 
 // ───────────────────────── session: the batched schedule as begin / samples / apply / finish ─────────────────────────
-// Single-GPU training is a loop over (samples, apply); multi-GPU training lets every rank produce the samples of
-// its slice of a batch's walks, exchanges the (centre, target, err) triples (RCCL all-gather, rank order = walk
-// order) and applies the full batch on every replica — the N-GPU result is bit-identical to the 1-GPU result.
+// Single-GPU training is a loop over (samples, apply); multi-GPU training lets every rank produce the samples of its slice of a
+// batch's walks and exchanges them by destination row (mn_n2v_shared.hpp) — the N-GPU result is bit-identical to the 1-GPU result.
 
-struct mn_n2v_session {
-    int device = 0;
-    N2vArgs a;
-    int B = 0, cap = 0, max_deg = 0, bits = 1;
-    size_t ns_max = 0, np_max = 0, tmp_bytes = 0;
-    // graph + model
-    int *off = nullptr, *adj = nullptr, *neg = nullptr;
-    float *syn0 = nullptr, *syn1 = nullptr, *sig = nullptr, *staged = nullptr;
-    // batch scratch
-    int *s_center = nullptr, *s_target = nullptr, *keys = nullptr, *vals = nullptr, *keys_s = nullptr, *vals_s = nullptr,
-        *keys_c = nullptr, *seg = nullptr, *seg_c = nullptr, *nseg = nullptr, *nseg_c = nullptr;
-    float *s_err = nullptr, *p_neu = nullptr;
-    int *p_center = nullptr;
-    double *cum = nullptr;
-    void *tmp = nullptr;
-    unsigned long long *pairs = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+// a base, so that the stream and the events are destroyed after the session's arrays are freed (as MnStreamEvents for the index)
+struct N2vStreamEvents {
     hipStream_t st = nullptr; // the session's own stream: every launch, memset, sort and exchange of a training run
-    ~mn_n2v_session() {
-        (void)hipFree(off); (void)hipFree(adj); (void)hipFree(neg); (void)hipFree(syn0); (void)hipFree(syn1); (void)hipFree(sig);
-        (void)hipFree(staged); (void)hipFree(s_center); (void)hipFree(s_target); (void)hipFree(keys); (void)hipFree(vals);
-        (void)hipFree(keys_s); (void)hipFree(vals_s); (void)hipFree(keys_c); (void)hipFree(seg); (void)hipFree(seg_c);
-        (void)hipFree(nseg); (void)hipFree(nseg_c); (void)hipFree(s_err); (void)hipFree(p_neu); (void)hipFree(p_center); (void)hipFree(cum); (void)hipFree(tmp); (void)hipFree(pairs);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~N2vStreamEvents() {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         if (st) (void)hipStreamDestroy(st);
     }
 };
 
-template <int NR>
-static int n2v_samples_t(mn_n2v_session *S, int epoch, int w, int lo, int hi, int *d_center, int *d_target, float *d_err,
-                         int *d_pcenter, float *d_pneu) {
+struct mn_n2v_session : N2vStreamEvents {
+    int device = 0;
+    N2vArgs a;
+    int B = 0, cap = 0, max_deg = 0, bits = 1;
+    size_t ns_max = 0, np_max = 0, tmp_bytes = 0;
+    DevArena mem; // owns every array below
+    // graph + model
+    int *off = nullptr, *adj = nullptr, *neg = nullptr;
+    float *syn0 = nullptr, *syn1 = nullptr, *sig = nullptr, *staged = nullptr;
+    unsigned long long *pairs = nullptr;
+    // batch scratch
+    int *s_center = nullptr, *s_target = nullptr, *keys = nullptr, *vals = nullptr, *keys_s = nullptr, *vals_s = nullptr,
+        *keys_c = nullptr, *seg = nullptr, *seg_c = nullptr;
+    float *s_err = nullptr, *p_neu = nullptr;
+    int *p_center = nullptr;
+    double *cum = nullptr; // running totals of the hubs' steps: [max_deg] sequential, [B][max_deg] batched
+    char *tmp = nullptr;   // the row sorts' scratch
+    int *walk = nullptr;   // sequential mode: a walk longer than N2V_LDS_WALK
+};
+
+// ends the session when a training entry point leaves, on whichever path
+struct N2vSessionEnd {
+    void operator()(mn_n2v_session *S) const { mn_n2v_end(S); }
+};
+using N2vSessionPtr = std::unique_ptr<mn_n2v_session, N2vSessionEnd>;
+
+// an array of the arena, or the unit's error string and -1
+template <typename T> static int n2v_alloc(DevArena &mem, T *&p, size_t count) {
+    p = mem.alloc<T>(count);
+    if (!p)
+        nset_err("node2vec: out of device memory (%zu bytes)", count * sizeof(T));
+    return p ? 0 : -1;
+}
+
+// calls f with the register slots per lane, NR >= ceil(dim / 64), as a compile-time constant: five widths cover dim <= 1024
+template <typename F> static auto n2v_for_width(int dim, F &&f) {
+    const int nr = (dim + 63) / 64;
+    if (nr <= 1) return f(std::integral_constant<int, 1>());
+    if (nr <= 2) return f(std::integral_constant<int, 2>());
+    if (nr <= 4) return f(std::integral_constant<int, 4>());
+    if (nr <= 8) return f(std::integral_constant<int, 8>());
+    return f(std::integral_constant<int, 16>());
+}
+
+static int n2v_samples(mn_n2v_session *S, int epoch, int w, int lo, int hi, int *d_center, int *d_target, float *d_err,
+                       int *d_pcenter, float *d_pneu) {
     N2vBatchArgs b;
     memset(&b, 0, sizeof(b));
     b.a = S->a;
@@ -504,21 +484,19 @@ static int n2v_samples_t(mn_n2v_session *S, int epoch, int w, int lo, int hi, in
     // enough wavefronts for several full rounds of the chip (8192 resident); the biased walk is too dear to repeat
     int split = uniform ? (32768 + (hi - lo) - 1) / (hi - lo) : 1;
     split = std::max(1, std::min(split, std::min(8, S->a.walk_length)));
-#ifdef MN_N2V_NO_SPLIT // timing experiments only
-    split = 1;
-#endif
     b.split = split;
     const size_t lds = (uniform ? 0 : N2VB_LDS_DEG * sizeof(double)) + (size_t)((S->a.walk_length + 3) & ~3) * sizeof(int) +
                        (N2V_SIG_SIZE + 1) * sizeof(float) + 64;
-    hipLaunchKernelGGL((k_n2v_walk_grad<NR>), dim3((unsigned)(hi - lo) * split), dim3(64), lds, S->st, b);
+    n2v_for_width(S->a.dim, [&](auto NR) {
+        hipLaunchKernelGGL((k_n2v_walk_grad<NR()>), dim3((unsigned)(hi - lo) * split), dim3(64), lds, S->st, b);
+    });
     NCHK(hipGetLastError());
     return 0;
 }
 
-template <int NR>
-static int n2v_apply_t(mn_n2v_session *S, const int *d_center, const int *d_target, const float *d_err, int64_t ns64,
-                       const int *d_pcenter, const float *d_pneu, int64_t np64, int row0, int row1) {
-    // rows [row0, row1): the destination rows this call updates (everything: 0, n; a rank of the data-parallel mode: its shard)
+// rows [row0, row1): the destination rows this call updates (everything: 0, n; a rank of the data-parallel mode: its shard)
+static int n2v_apply(mn_n2v_session *S, const int *d_center, const int *d_target, const float *d_err, int64_t ns64,
+                     const int *d_pcenter, const float *d_pneu, int64_t np64, int row0 = 0, int row1 = 0x7fffffff) {
     const N2vArgs &a = S->a;
     const int N = a.n, dim = a.dim;
     row1 = std::min(row1, N);
@@ -544,8 +522,10 @@ static int n2v_apply_t(mn_n2v_session *S, const int *d_center, const int *d_targ
         NCHK(hipMemsetAsync(S->seg_c, 0xFF, (size_t)N * sizeof(int), S->st));
         hipLaunchKernelGGL(k_n2v_segments, dim3(p256), dim3(256), 0, S->st, S->keys_c, np, N, S->seg_c);
         if (nrows)
-            hipLaunchKernelGGL((k_n2v_apply_centers<NR>), dim3(nrows), dim3(64), 0, S->st, S->keys_c, S->vals_s, S->seg_c, np, d_pneu,
-                               a.syn0, S->staged, dim, row0);
+            n2v_for_width(dim, [&](auto NR) {
+                hipLaunchKernelGGL((k_n2v_apply_centers<NR()>), dim3(nrows), dim3(64), 0, S->st, S->keys_c, S->vals_s, S->seg_c, np,
+                                   d_pneu, a.syn0, S->staged, dim, row0);
+            });
     }
     if (ns > 0) {
         // targets: syn1neg[t] += Σ err · syn0_old[c]  (syn0 is still the old one) → in place
@@ -558,87 +538,13 @@ static int n2v_apply_t(mn_n2v_session *S, const int *d_center, const int *d_targ
         NCHK(hipMemsetAsync(S->seg, 0xFF, (size_t)N * sizeof(int), S->st));
         hipLaunchKernelGGL(k_n2v_segments, dim3(g256), dim3(256), 0, S->st, S->keys_s, ns, N, S->seg);
         if (nrows)
-            hipLaunchKernelGGL((k_n2v_apply<NR>), dim3(nrows), dim3(64), 0, S->st, S->keys_s, S->vals_s, S->seg, ns, d_center, d_err,
-                               a.syn1neg, a.syn0, a.syn1neg, dim, row0);
+            n2v_for_width(dim, [&](auto NR) {
+                hipLaunchKernelGGL((k_n2v_apply<NR()>), dim3(nrows), dim3(64), 0, S->st, S->keys_s, S->vals_s, S->seg, ns, d_center,
+                                   d_err, a.syn1neg, a.syn0, a.syn1neg, dim, row0);
+            });
     }
     if (np > 0 && nrows)
         hipLaunchKernelGGL(k_n2v_commit, dim3(nrows), dim3(64), 0, S->st, S->seg_c, S->staged, a.syn0, dim, row0);
     NCHK(hipGetLastError());
     return 0;
-}
-
-// ── data-parallel exchange by destination shard (mn_node2vec_train_shared) ──
-// A rank's samples are wanted by ONE rank each: the one that owns the sample's target row (positions: the centre row).  Instead of
-// all-gathering everything to everybody, a rank sorts its slots by destination shard — a stable one-pass radix sort, so every
-// bucket keeps the walk order —, packs the buckets and exchanges them all-to-all: 1 / world of the bytes on the links, and each
-// rank sorts and applies 1 / world of the samples.  Received buckets stand in source-rank order = the batch's walk order, so a
-// row's additions are the ones, in the order, that one GPU makes.
-__global__ void k_n2v_shard_keys(const int *dest, int n, int rows_per, int world, int *keys, int *vals, int *hist) {
-    __shared__ int h[65];
-    for (int i = threadIdx.x; i <= world; i += blockDim.x)
-        h[i] = 0;
-    __syncthreads();
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (size_t)n) {
-        const int d = dest[i];
-        const int k = d < 0 ? world : d / rows_per; // (unused slot: sorts to the end, is not sent)
-        keys[i] = k;
-        vals[i] = (int)i;
-        atomicAdd(&h[k], 1);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i <= world; i += blockDim.x)
-        if (h[i])
-            atomicAdd(&hist[i], h[i]);
-}
-__global__ void k_n2v_pack_samples(const int *order, int n, const int *c, const int *t, const float *e, int *out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n)
-        return;
-    const int j = order[i];
-    out[3 * i] = c[j];
-    out[3 * i + 1] = t[j];
-    out[3 * i + 2] = __float_as_int(e[j]);
-}
-__global__ void k_n2v_unpack_samples(const int *in, int n, int *c, int *t, float *e) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n)
-        return;
-    c[i] = in[3 * i];
-    t[i] = in[3 * i + 1];
-    e[i] = __int_as_float(in[3 * i + 2]);
-}
-// a position travels as one record: its centre, then its neu1e vector
-__global__ void __launch_bounds__(64) k_n2v_pack_positions(const int *order, const int *pc, const float *pn, int dim, float *out) {
-    const int j = order[blockIdx.x];
-    float *o = out + (size_t)blockIdx.x * (dim + 1);
-    if (threadIdx.x == 0)
-        o[0] = __int_as_float(pc[j]);
-    for (int d = threadIdx.x; d < dim; d += 64)
-        o[1 + d] = pn[(size_t)j * dim + d];
-}
-__global__ void __launch_bounds__(64) k_n2v_unpack_positions(const float *in, int dim, int *pc, float *pn) {
-    const float *r = in + (size_t)blockIdx.x * (dim + 1);
-    if (threadIdx.x == 0)
-        pc[blockIdx.x] = __float_as_int(r[0]);
-    for (int d = threadIdx.x; d < dim; d += 64)
-        pn[(size_t)blockIdx.x * dim + d] = r[1 + d];
-}
-
-#define N2V_DISPATCH(fn, ...)                                         \
-    do {                                                              \
-        const int nr__ = (S->a.dim + 63) / 64;                        \
-        if (nr__ <= 1) return fn<1>(__VA_ARGS__);                     \
-        if (nr__ <= 2) return fn<2>(__VA_ARGS__);                     \
-        if (nr__ <= 4) return fn<4>(__VA_ARGS__);                     \
-        if (nr__ <= 8) return fn<8>(__VA_ARGS__);                     \
-        return fn<16>(__VA_ARGS__);                                   \
-    } while (0)
-
-static int n2v_samples(mn_n2v_session *S, int epoch, int w, int lo, int hi, int *c, int *t, float *e, int *pc, float *pn) {
-    N2V_DISPATCH(n2v_samples_t, S, epoch, w, lo, hi, c, t, e, pc, pn);
-}
-static int n2v_apply(mn_n2v_session *S, const int *c, const int *t, const float *e, int64_t ns, const int *pc, const float *pn,
-                     int64_t np, int row0 = 0, int row1 = 0x7fffffff) {
-    N2V_DISPATCH(n2v_apply_t, S, c, t, e, ns, pc, pn, np, row0, row1);
 }

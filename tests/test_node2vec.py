@@ -42,7 +42,7 @@ def _dead_end_graph(n=203, seed=5):
 
 
 def _n2v_template(dim):
-    """N2V_DISPATCH (csrc/mn_n2v_batched.hpp) → (NR register slots per lane, PF target rows in flight per chunk in
+    """n2v_for_width (csrc/mn_n2v_batched.hpp) → (NR register slots per lane, PF target rows in flight per chunk in
     k_n2v_walk_grad, U source rows in flight in k_n2v_apply)"""
     nr = (dim + 63) // 64
     NR = next(t for t in (1, 2, 4, 8, 16) if nr <= t)
@@ -50,7 +50,7 @@ def _n2v_template(dim):
 
 
 def _n2v_split(p, q, walk_length, walks):
-    """wavefronts that share one walk in k_n2v_walk_grad (n2v_samples_t), for a batch of `walks` walks"""
+    """wavefronts that share one walk in k_n2v_walk_grad (n2v_samples), for a batch of `walks` walks"""
     split = -(-32768 // walks) if p == 1.0 and q == 1.0 else 1
     return max(1, min(split, 8, walk_length))
 
@@ -147,7 +147,7 @@ def test_live_reference_star_2049_leaves():
 
 
 def test_width_cases_cover_every_template_and_chunk_shape():
-    """WIDTHS reaches every instantiation of N2V_DISPATCH, each with a run of full chunks only and one that ends in a
+    """WIDTHS reaches every instantiation of n2v_for_width, each with a run of full chunks only and one that ends in a
     partial chunk; SPLITS reaches split 1, 2, 3 and 8."""
     seen = set()
     for dim, p, q, neg in WIDTHS:
