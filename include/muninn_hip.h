@@ -422,6 +422,54 @@ int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, const int *see
  * parent (-1 for a seed) of each, row count as returned; any pointer may be NULL.  0 / -1. */
 int mn_graph_bfs_rows(mn_graph *g, int *node, int *depth, int *parent);
 
+/* ---- graph_select: the lineage selectors (src/graph_selector_parse.c, src/graph_selector_eval.c) ---- */
+typedef enum {
+    MN_SEL_NODE = 0,        /* x       direction "self" */
+    MN_SEL_ANCESTORS = 1,   /* N+x     "ancestor" */
+    MN_SEL_DESCENDANTS = 2, /* x+M     "descendant" */
+    MN_SEL_BOTH = 3,        /* N+x+M   "both" */
+    MN_SEL_CLOSURE = 4,     /* @x      "closure" */
+    MN_SEL_UNION = 5,       /* a b     "selected", as the two below */
+    MN_SEL_INTERSECT = 6,   /* a,b */
+    MN_SEL_COMPLEMENT = 7   /* not a */
+} mn_select_opcode;
+typedef struct {
+    int op;                   /* mn_select_opcode */
+    int node;                 /* atoms: the node's index; -1 as parsed, the caller resolves the name */
+    int depth_up, depth_down; /* atoms: the limits, -1 = none */
+    int name_off, name_len;   /* atoms: where the name stands in the parsed text */
+} mn_select_op;
+typedef struct {
+    int64_t rows, levels, launches, syncs, bottom_up_levels; /* levels: level launches that had a frontier to expand; launches: all
+                                                                level launches; syncs: status read-backs, one per group of levels */
+    double device_ms;
+} mn_select_stats;
+/* selector_parse (src/graph_selector_parse.c:467-510) as a postfix program: the atoms stand in source order, a set operator
+ * after its operands (union by juxtaposition and intersection by comma are left-associative, `not` binds one atom).  A caller
+ * that resolves the atoms' names in program order and stops at the first it does not know reports the node the reference
+ * reports.  Same tokens and quirks as the reference: names start with an ASCII letter, digit or '_' and go on with those, '.'
+ * and '-'; `not` is a name where the text ends or a comma follows; an all-digit token is a depth only in front of '+'; a '+'
+ * after a name is its suffix only if an integer, the end or a comma follows; `@+x` and `@x+` are `@x`.  A depth beyond INT_MAX
+ * is INT_MAX (the reference's int overflows there).  *prog is malloc'ed: mn_host_free.  Touches no device.  Returns 0, or -1 with
+ * mn_graph_last_error holding the reference's message ("graph_select: empty selector expression", "… unexpected character
+ * '%c' at position %d", "… expected node name at position %d", "… unexpected token at position %d"). */
+int mn_select_parse(const char *expr, mn_select_op **prog, int *n_ops);
+/* selector_eval (src/graph_selector_eval.c:511-543) on the device over the handle's out- and in-lists as they are (the graph must
+ * hold both: graph_select loads its table with direction "both").  The rows are the selected nodes in ascending index with
+ * their depth: the hop distance the ROOT operator's traversal found (0 for every row when the root is a set operator, and for
+ * every descendant under `@x`).  A limit on `N+x` / `x+M` under a set operator is ignored unless it is 0, as in the reference;
+ * `N+x+M` honours its limits everywhere, and its descendant pass neither reports nor walks through what its ancestor pass found.
+ * A stack machine over n-bit sets (csrc/mn_select.hip): level-synchronous traversals with bitmap frontiers, one launch per level,
+ * top-down or bottom-up per level — MN_SELECT_BOTTOM_UP = 0 | 1 | auto (default: bottom-up when the frontier holds more than
+ * 1 / MN_SELECT_BOTTOM_UP_DIV of the direction's list entries) — and MN_SELECT_LEVELS_PER_SYNC level launches queued per status
+ * read-back; all three are read at each call and change no row.  A node outside 0 .. n - 1, an operator without its operands or
+ * a program that does not leave one set is an error before any launch.  The scratch (a few n-bit sets, three int32[n]) stays with the
+ * handle until mn_graph_destroy.  stats may be NULL.  Sets mn_graph_last_ms.  Returns the row count, or -1 with
+ * mn_graph_last_error set. */
+int64_t mn_graph_select(mn_graph *g, const mn_select_op *prog, int n_ops, mn_select_stats *stats);
+/* The rows of the last mn_graph_select on this handle: node and depth of each, row count as returned; either may be NULL.  0 / -1. */
+int mn_graph_select_rows(mn_graph *g, int *node, int *depth);
+
 /* ---- node2vec.c replacements (a14-a17) ---- */
 typedef struct {
     int dim;            /* 1..1024 (src/node2vec.c:447) */

@@ -23,6 +23,21 @@ class BfsStats(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class SelectOp(C.Structure):
+    _fields_ = [("op", C.c_int), ("node", C.c_int), ("depth_up", C.c_int), ("depth_down", C.c_int), ("name_off", C.c_int),
+                ("name_len", C.c_int)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("levels", C.c_int64), ("launches", C.c_int64), ("syncs", C.c_int64),
+                ("bottom_up_levels", C.c_int64), ("device_ms", C.c_double)]
+
+
+SEL_NODE, SEL_ANCESTORS, SEL_DESCENDANTS, SEL_BOTH, SEL_CLOSURE, SEL_UNION, SEL_INTERSECT, SEL_COMPLEMENT = range(8)
+SELECT_LEVELS_PER_SYNC = 16  # the library's default for MN_SELECT_LEVELS_PER_SYNC (csrc/mn_select.hip)
+SEL_DIRECTIONS = ("self", "ancestor", "descendant", "both", "closure", "selected", "selected", "selected")
+
+
 class N2vParams(C.Structure):
     _fields_ = [("dim", C.c_int), ("p", C.c_double), ("q", C.c_double), ("num_walks", C.c_int), ("walk_length", C.c_int),
                 ("window", C.c_int), ("neg_samples", C.c_int), ("learning_rate", C.c_double), ("epochs", C.c_int),
@@ -77,6 +92,9 @@ GRAPH_SYMBOLS = [
     ("mn_graph_bfs", C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
                                  np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(BfsStats)]),
     ("mn_graph_bfs_rows", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
+    ("mn_select_parse", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(SelectOp)), C.POINTER(C.c_int)]),
+    ("mn_graph_select", C.c_int64, [C.c_void_p, C.POINTER(SelectOp), C.c_int, C.POINTER(SelectStats)]),
+    ("mn_graph_select_rows", C.c_int, [C.c_void_p, _i32p, _i32p]),
     ("mn_graph_pagerank", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_double, C.c_int, C.c_int,
                                     np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), C.POINTER(AlgoStats)]),
     ("mn_graph_components", C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(AlgoStats)]),
@@ -203,6 +221,51 @@ class Graph:
         """graph_bfs's rows from one start node → (node, depth, parent) int32 arrays; self.bfs_stats as for bfs_batch"""
         return self.bfs_batch([seed], max_depth, direction)[1:]
 
+    def select_program(self, prog):
+        """selector_eval (src/graph_selector_eval.c:511-543) for a resolved program, a list of (op, node, depth_up,
+        depth_down) → (node, depth) int32 arrays in ascending node index; self.select_stats afterwards"""
+        ops = (SelectOp * max(1, len(prog)))()
+        for i, (op, node, up, down) in enumerate(prog):
+            ops[i] = SelectOp(int(op), int(node), int(up), int(down), 0, 0)
+        st = SelectStats()
+        rows = self.L.mn_graph_select(self.h, ops, len(prog), C.byref(st))
+        if rows < 0:
+            raise MuninnHipError(_gerr())
+        out = [np.empty(max(rows, 1), np.int32) for _ in range(2)]
+        if self.L.mn_graph_select_rows(self.h, *out) != 0:
+            raise MuninnHipError(_gerr())
+        self.select_stats = {n: getattr(st, n) for n, _ in SelectStats._fields_}
+        return tuple(a[:rows] for a in out)
+
+    def select(self, expr, names=None):
+        """graph_select's rows for a selector expression → (node int32, depth int32, direction str).  names: the node ids by
+        index, as the edge table gave them, or a function from a name's bytes to its index (-1: no such node); None → a
+        node's name is its index in decimal.  ValueError carries the reference's message: a syntax error, or the first
+        name, left to right, that is no node."""
+        prog = select_parse(expr)
+        if self.n == 0:  # selector_eval answers an empty graph before it looks anything up (:514)
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), SEL_DIRECTIONS[prog[-1][0]]
+        index = None if names is None or callable(names) else {}
+        for i, nm in enumerate(() if index is None else names):
+            index.setdefault(nm.encode() if isinstance(nm, str) else bytes(nm), i)
+        resolved = []
+        for op, name, up, down in prog:
+            node = -1
+            if op <= SEL_CLOSURE:
+                if index is not None:
+                    node = index.get(name, -1)
+                elif callable(names):
+                    node = int(names(name))
+                    node = node if 0 <= node < self.n else -1
+                elif name.isdigit() and name == b"%d" % int(name) and int(name) < self.n:
+                    node = int(name)
+                if node < 0:
+                    msg = b"graph_select: node '" + name + b"' not found"
+                    raise ValueError(msg[:255].decode("utf-8", "replace"))  # snprintf into 256 bytes (:287)
+            resolved.append((op, node, up, down))
+        node, depth = self.select_program(resolved)
+        return node, depth, SEL_DIRECTIONS[prog[-1][0]]
+
     def shortest_path_unweighted(self, start, end):
         """run_shortest_path_bfs (src/graph_tvf.c:472-586): a forward BFS from start whose first-discovery parents are
         traced back from end on the host → the nodes of the path, start first, or [] when end is not reached."""
@@ -219,6 +282,22 @@ class Graph:
         st = LeidenStats()
         self.L.mn_graph_leiden_stats(self.h, C.byref(st))
         return comm[:self.n], q.value, {n: getattr(st, n) for n, _ in LeidenStats._fields_}
+
+
+def select_parse(expr):
+    """selector_parse (src/graph_selector_parse.c) → the postfix program as a list of (op, name bytes or None, depth_up,
+    depth_down), atoms in source order.  ValueError carries the reference's message.  Touches no device."""
+    L = _glib()
+    raw = expr.encode("utf-8", "surrogateescape") if isinstance(expr, str) else bytes(expr)
+    raw = raw.split(b"\0", 1)[0]  # a C string ends at its first NUL
+    prog, n = C.POINTER(SelectOp)(), C.c_int(0)
+    if L.mn_select_parse(raw, C.byref(prog), C.byref(n)) != 0:
+        raise ValueError((L.mn_graph_last_error() or b"").decode("utf-8", "surrogateescape"))
+    try:
+        return [(o.op, raw[o.name_off:o.name_off + o.name_len] if o.op <= SEL_CLOSURE else None, o.depth_up, o.depth_down)
+                for o in (prog[i] for i in range(n.value))]
+    finally:
+        L.mn_host_free(prog)
 
 
 def trace_path(node, parent, start, end):
