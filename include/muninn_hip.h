@@ -422,6 +422,47 @@ int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, const int *see
  * parent (-1 for a seed) of each, row count as returned; any pointer may be NULL.  0 / -1. */
 int mn_graph_bfs_rows(mn_graph *g, int *node, int *depth, int *parent);
 
+/* ---- graph_shortest_path (src/graph_tvf.c:472-753) ---- */
+typedef enum {
+    MN_SP_AUTO = 0,      /* replay when the graph holds a negative weight or E_out + 1 <= MN_SP_REPLAY_MAX (4096), else fast */
+    MN_SP_REPLAY = 1,    /* run_shortest_path_dijkstra (:600-753) as written, one wavefront per pair: the reference's rows */
+    MN_SP_FAST = 2,      /* label-correcting SSSP per distinct start: the reference's distances, canonical parents */
+    MN_SP_UNWEIGHTED = 3 /* never asked for, only reported in mn_sp_stats.mode_used: run_shortest_path_bfs (:472-586) */
+} mn_sp_mode;
+typedef struct {
+    int mode_used, chunks, sources; /* sources: distinct starts (fast, unweighted) or pairs (replay) */
+    int64_t pops, pushes;           /* replay: queue entries popped (:651-653) and appended (:691-694) */
+    int64_t relaxations, passes;    /* fast: list entries relaxed, frontier passes (each one host round trip); unweighted: the
+                                       traversals' edges_scanned and levels */
+    double device_ms;
+} mn_sp_stats;
+/* graph_shortest_path's search (src/graph_tvf.c:472-753) for n_pairs (start[i], end[i]) pairs over the handle's out-lists: per
+ * pair the rows (node, distance) of one shortest path, start first; no path → no rows; start == end → the one row (start, 0.0).
+ * row_off[n_pairs + 1]: pair i's rows are row_off[i] .. row_off[i + 1] - 1 of mn_graph_shortest_paths_rows, and a row's
+ * path_order (:730) is its place within the pair.
+ *   weighted == 0, or a graph without weights: run_shortest_path_bfs (:472-586), first-discovery parents of one mn_graph_bfs
+ *     traversal per distinct start (which replaces the rows of the handle's last mn_graph_bfs); distance = place on the path.
+ *   MN_SP_REPLAY: run_shortest_path_dijkstra (:600-753) verbatim — array queue, first index of the strict minimum popped,
+ *     last entry into the hole, stale pops dropped, unsettled targets appended in list order — one wavefront per pair.  Every
+ *     tie, every finite negative weight and +inf come out as the reference's.  O(pops x queue / 64) per pair.  Scratch per
+ *     pair: 16 bytes per (E_out + 1) queue entries and 12 per node.
+ *   MN_SP_FAST: weights must be >= 0.  The distances are the reference's bit for bit (with weights >= 0 the fixpoint of
+ *     dist[v] = min fl(dist[u] + w) does not depend on the order of relaxations); the path is the canonical one: fewest edges
+ *     among the shortest paths, then at each node the parent with the lowest (index, place in its list).  Where only one
+ *     shortest path exists that is the reference's.  A start's search ends once all of its ends are final.  Scratch: 40 bytes
+ *     per node per distinct start of a chunk.  MN_SSSP_DELTA (a distance, `inf` = plain frontier Bellman-Ford; default: the
+ *     mean finite weight) sets the near/far threshold step and changes no output bit, nor does the chunking.
+ * Pairs (replay) or distinct starts (fast) go through in chunks under a scratch budget: half of the free device memory, or
+ * MN_SP_SCRATCH_MB MiB (fractions allowed), at least one at a time.  A NaN or -inf weight is refused in every weighted mode, a
+ * negative weight in MN_SP_FAST; an index outside 0 .. n - 1, n_pairs < 0, a graph that holds only in-lists or n > 2^26 is
+ * an error before any launch.  stats may be NULL.  Sets mn_graph_last_ms.  Returns the row count, or -1 with
+ * mn_graph_last_error set. */
+int64_t mn_graph_shortest_paths(mn_graph *g, int mode, int weighted, int64_t n_pairs, const int *start, const int *end,
+                                int64_t *row_off, mn_sp_stats *stats);
+/* The rows of the last mn_graph_shortest_paths on this handle (they stay with it until the next call or mn_graph_destroy), the
+ * PathRow fields node and distance (:424-428, :729-731); either pointer may be NULL.  0 / -1. */
+int mn_graph_shortest_paths_rows(mn_graph *g, int *node, double *distance);
+
 /* ---- graph_select: the lineage selectors (src/graph_selector_parse.c, src/graph_selector_eval.c) ---- */
 typedef enum {
     MN_SEL_NODE = 0,        /* x       direction "self" */

@@ -5,7 +5,7 @@
  * (:876-887 — so `direction='both'` without `max_depth` lands in max_depth, reads as 0 and answers the start row), defaults
  * (max_depth 100, direction 'forward'), the two error strings, rows in queue order with rowid = position.  The SQL ingest is
  * mn_sql_load_graph (text ids → first-seen indices, lists in table-row order, rows with a NULL endpoint skipped); the traversal
- * is mn_graph_bfs.  graph_dfs and graph_shortest_path are not registered.
+ * is mn_graph_bfs.  graph_shortest_path is mn_path_tvf.c's; graph_dfs is not registered.
  *
  * A translation unit of its own: the integrated build (oracle/Makefile) links the reference's graph_tvf.c, which registers
  * its own graph_bfs, next to this repository's other extension sources — nothing of theirs refers to this file.

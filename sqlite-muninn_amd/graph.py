@@ -23,6 +23,15 @@ class BfsStats(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class SpStats(C.Structure):
+    _fields_ = [("mode_used", C.c_int), ("chunks", C.c_int), ("sources", C.c_int), ("pops", C.c_int64), ("pushes", C.c_int64),
+                ("relaxations", C.c_int64), ("passes", C.c_int64), ("device_ms", C.c_double)]
+
+
+SP_AUTO, SP_REPLAY, SP_FAST, SP_UNWEIGHTED = range(4)
+SP_MODES = {"auto": SP_AUTO, "replay": SP_REPLAY, "exact": SP_REPLAY, "fast": SP_FAST}
+
+
 class SelectOp(C.Structure):
     _fields_ = [("op", C.c_int), ("node", C.c_int), ("depth_up", C.c_int), ("depth_down", C.c_int), ("name_off", C.c_int),
                 ("name_len", C.c_int)]
@@ -92,6 +101,9 @@ GRAPH_SYMBOLS = [
     ("mn_graph_bfs", C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
                                  np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(BfsStats)]),
     ("mn_graph_bfs_rows", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
+    ("mn_graph_shortest_paths", C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                            np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(SpStats)]),
+    ("mn_graph_shortest_paths_rows", C.c_int, [C.c_void_p, _i32p, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]),
     ("mn_select_parse", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(SelectOp)), C.POINTER(C.c_int)]),
     ("mn_graph_select", C.c_int64, [C.c_void_p, C.POINTER(SelectOp), C.c_int, C.POINTER(SelectStats)]),
     ("mn_graph_select_rows", C.c_int, [C.c_void_p, _i32p, _i32p]),
@@ -266,11 +278,37 @@ class Graph:
         node, depth = self.select_program(resolved)
         return node, depth, SEL_DIRECTIONS[prog[-1][0]]
 
+    def shortest_paths(self, starts, ends, weighted=True, mode="auto"):
+        """graph_shortest_path's search (src/graph_tvf.c:472-753) for the pairs (starts[i], ends[i]) at once → (row_off
+        [len(starts) + 1] int64, node int32, distance float64): pair i's path, start first, is rows row_off[i] ..
+        row_off[i + 1] - 1 (none when end is not reached).  mode "replay" (or "exact") gives the reference's rows, "fast" its
+        distances and the canonical path, "auto" chooses (include/muninn_hip.h); weighted=False, or a graph without weights,
+        is the reference's BFS half.  The call's statistics are in self.sp_stats afterwards."""
+        starts = np.ascontiguousarray(starts, np.int32).reshape(-1)
+        ends = np.ascontiguousarray(ends, np.int32).reshape(-1)
+        if len(starts) != len(ends):
+            raise ValueError("shortest_paths: starts and ends differ in length")
+        row_off = np.zeros(len(starts) + 1, np.int64)
+        st = SpStats()
+        rows = self.L.mn_graph_shortest_paths(self.h, SP_MODES[mode], int(bool(weighted)), len(starts),
+                                              starts.ctypes.data if len(starts) else None, ends.ctypes.data if len(ends) else None,
+                                              row_off, C.byref(st))
+        if rows < 0:
+            raise MuninnHipError(_gerr())
+        node, dist = np.empty(max(rows, 1), np.int32), np.empty(max(rows, 1), np.float64)
+        if self.L.mn_graph_shortest_paths_rows(self.h, node, dist) != 0:
+            raise MuninnHipError(_gerr())
+        self.sp_stats = {n: getattr(st, n) for n, _ in SpStats._fields_}
+        return row_off, node[:rows], dist[:rows]
+
+    def shortest_path(self, start, end, weighted=True, mode="auto"):
+        """one pair of shortest_paths → (node int32, distance float64), empty when end is not reached"""
+        return self.shortest_paths([start], [end], weighted, mode)[1:]
+
     def shortest_path_unweighted(self, start, end):
-        """run_shortest_path_bfs (src/graph_tvf.c:472-586): a forward BFS from start whose first-discovery parents are
-        traced back from end on the host → the nodes of the path, start first, or [] when end is not reached."""
-        node, _, parent = self.bfs(start, max_depth=2**31 - 1, direction="forward")
-        return trace_path(node, parent, start, end)
+        """run_shortest_path_bfs (src/graph_tvf.c:472-586): the first-discovery parents of a forward BFS from start, traced
+        back from end → the nodes of the path, start first, or [] when end is not reached."""
+        return [int(v) for v in self.shortest_path(start, end, weighted=False)[0]]
 
     def leiden(self, resolution=1.0, direction="both", mode=LEIDEN_SEQUENTIAL, batch=0):
         """run_leiden → (community[n] int32, Q, stats dict)"""
@@ -298,17 +336,6 @@ def select_parse(expr):
                 for o in (prog[i] for i in range(n.value))]
     finally:
         L.mn_host_free(prog)
-
-
-def trace_path(node, parent, start, end):
-    """the path start .. end through a BFS's (node, parent) rows, or [] when end is not among them"""
-    up = {int(v): int(p) for v, p in zip(node, parent)}
-    if int(end) not in up:
-        return []
-    path = [int(end)]
-    while path[-1] != int(start):
-        path.append(up[path[-1]])
-    return path[::-1]
 
 
 def node2vec_train(off, adj, dim, p=1.0, q=1.0, num_walks=10, walk_length=80, window=5, neg_samples=5, learning_rate=0.025,
