@@ -350,6 +350,23 @@ typedef struct {
     int weights_bytes;
 } mn_csr_block;
 mn_graph *mn_graph_create_blocked(int n_nodes, const mn_csr_block *fwd, int n_fwd, const mn_csr_block *rev, int n_rev, int device);
+/* The same graph from an edge list with integer node indices, built on the device (csrc/mn_csr_build.hip): what the
+ * reference's ingest loop (src/graph_load.c:227-246) and csr_build (src/graph_csr.c:20-83) make on the host.  out[src] lists
+ * dst and in[dst] lists src, each in edge ROW order; weights (NULL = unweighted) are copied bit for bit.  lists: 1 = out,
+ * 2 = in, 3 = both; a list not asked for is empty, as if mn_graph_create had been given empty lists.  The result is an
+ * ordinary handle (weighted, edge counts, maximum degrees, host offset copies).  n_rows == 0 is a graph of empty lists.
+ * Two implementations give the same bytes: one stable rocprim radix sort of (node, row number) (MN_CSR_BUILD=radix, the
+ * default: the faster one on the benchmark graph) and, with MN_CSR_BUILD=sort, per-list sorts of row numbers binned by degree
+ * (the bin limits are read per call from MN_CSR_SORT_WAVE, at most 64, and MN_CSR_SORT_LDS, at most 8192).  An index outside 0 .. n_nodes - 1 (found on the device before anything is
+ * written through it), n_rows < 0, n_rows >= 2^31 - 1 or n_nodes < 0 is an error: NULL with mn_graph_last_error set.  Sets
+ * mn_graph_last_ms (first kernel to last, the offsets' read-back between them included; the uploads are outside). */
+mn_graph *mn_graph_from_edges(int n_nodes, int64_t n_rows, const int *src, const int *dst, const double *w, int lists, int device);
+/* One direction of the handle as csr_build leaves it on the host (which: 0 = out, 1 = in): off[n_nodes + 1], tgt[edges],
+ * w[edges]; tgt and w may be NULL, and w is written only where the graph holds weights for that direction.  Returns 1 when
+ * it does, 0 when it does not, -1 on error. */
+int mn_graph_export_csr(mn_graph *g, int which, int *off, int *tgt, double *w);
+/* A second owner: every mn_graph_retain is paid for by one more mn_graph_destroy, and the last one frees. */
+void mn_graph_retain(mn_graph *g);
 void mn_graph_destroy(mn_graph *g);
 const char *mn_graph_last_error(void);
 

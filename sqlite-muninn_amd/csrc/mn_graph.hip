@@ -175,8 +175,13 @@ extern "C" mn_graph *mn_graph_create_blocked(int n_nodes, const mn_csr_block *fw
     return g;
 } MN_GUARD_END(gset_err, MN_NOTHING, nullptr)
 
+extern "C" void mn_graph_retain(mn_graph *g) {
+    if (g)
+        g->refs.fetch_add(1, std::memory_order_relaxed);
+}
+
 extern "C" void mn_graph_destroy(mn_graph *g) {
-    if (!g)
+    if (!g || g->refs.fetch_sub(1, std::memory_order_acq_rel) > 1)
         return;
     (void)hipSetDevice(g->device);
     if (g->stream)

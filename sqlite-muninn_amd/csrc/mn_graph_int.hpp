@@ -1,4 +1,5 @@
 // mn_graph_int.hpp — what the translation units behind the mn_graph handle share: mn_graph.hip (handle, CSR upload),
+// mn_csr_build.hip (the handle built on the device from an edge list),
 // mn_leiden.hip (with mn_leiden_eval.hpp, the device code of its evaluation, included by it alone), mn_centrality.hip and
 // mn_bfs.hip, mn_select.hip and mn_sssp.hip.  Host declarations and the kernels' view of the CSR only: device code does not cross a translation unit, every
 // kernel lives in the file that launches it.
@@ -7,6 +8,7 @@
 #include "mn_host.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #define DEVI __device__ __forceinline__
@@ -25,6 +27,7 @@ struct SelWork; // mn_select.hip
 struct SpWork;  // mn_sssp.hip
 
 struct mn_graph {
+    std::atomic<int> refs{1}; // owners: mn_graph_retain adds one, mn_graph_destroy releases one and the last frees
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -413,6 +413,13 @@ static void adj_free_blocks(mn_csr_block *b, int n) {
     free(b);
 }
 
+/* Where the graph_adjacency module of this extension is linked in (mn_adjacency_vtab.c; an integrated build links this file
+ * without it, hence weak), the device graph of a fresh table may still be in HBM from the last rebuild or the last call:
+ * mn_adj_resident hands out a retained handle and a copy of the ids, or NULL for "load the blocks"; what was loaded then is
+ * offered back.  MUNINN_ADJ_RESIDENT=0 makes both do nothing. */
+mn_graph *mn_adj_resident(sqlite3 *db, const char *name, char ***ids_out, int *n_out) __attribute__((weak));
+void mn_adj_resident_offer(sqlite3 *db, const char *name, mn_graph *g, char *const *ids, int n) __attribute__((weak));
+
 /* the stored CSR of a fresh graph_adjacency table → device graph + node ids; *ids_out owns malloc'd strings */
 static mn_graph *adj_load_fresh(sqlite3 *db, const char *t, char ***ids_out, int *n_out, char **err) {
     char *sql = sqlite3_mprintf("SELECT id FROM \"%w_nodes\" ORDER BY idx", t);
@@ -507,7 +514,18 @@ int mn_sql_load_graph(sqlite3 *db, const char *who, const char *edge_table, cons
             sqlite3_free(a_table);
             char **ids = 0, *e2 = 0;
             int n = 0;
-            mn_graph *g = adj_load_fresh(db, edge_table, &ids, &n, &e2);
+            mn_graph *g = mn_adj_resident ? mn_adj_resident(db, edge_table, &ids, &n) : 0;
+            if (g) {
+                *g_out = g;
+                *ids_out = ids;
+                *n_out = n;
+                return SQLITE_OK;
+            }
+            ids = 0;
+            n = 0;
+            g = adj_load_fresh(db, edge_table, &ids, &n, &e2);
+            if (g && mn_adj_resident_offer)
+                mn_adj_resident_offer(db, edge_table, g, ids, n);
             if (!g) {
                 for (int i = 0; i < n; i++)
                     free(ids[i]);

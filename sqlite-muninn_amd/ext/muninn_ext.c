@@ -8,7 +8,8 @@
  * `graph_leiden` — and §8 f-4's `graph_components` / `graph_pagerank` / `graph_node_betweenness` / `graph_edge_betweenness` /
  * `graph_degree` / `graph_closeness`, the reference's `graph_bfs` (src/graph_tvf.c:230-309; mn_traverse_tvf.c), its
  * `graph_shortest_path` (src/graph_tvf.c:472-753; mn_path_tvf.c), its `graph_select` (src/graph_select_tvf.c;
- * mn_select_tvf.c) and its `muninn_extract_er` (src/llama_er.c), each backed by libmuninn_hip.so (include/muninn_hip.h).
+ * mn_select_tvf.c), its `muninn_extract_er` (src/llama_er.c) and its `graph_adjacency` virtual table (src/graph_adjacency.c;
+ * mn_adjacency_vtab.c), each backed by libmuninn_hip.so (include/muninn_hip.h).
  */
 #include "mn_sqlite_abi.h"
 
@@ -23,6 +24,7 @@ int mn_register_path_tvf(sqlite3 *db) __attribute__((weak));
 int mn_register_betweenness_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_centrality_tvfs(sqlite3 *db) __attribute__((weak));
 int mn_register_er_functions(sqlite3 *db) __attribute__((weak));
+int mn_register_adjacency_module(sqlite3 *db) __attribute__((weak));
 
 #ifdef _WIN32
 __declspec(dllexport)
@@ -87,6 +89,13 @@ int sqlite3_muninn_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
         rc = mn_register_er_functions(db);
         if (rc != SQLITE_OK) {
             *pzErrMsg = sqlite3_mprintf("muninn: failed to register entity resolution functions");
+            return rc;
+        }
+    }
+    if (mn_register_adjacency_module) {
+        rc = mn_register_adjacency_module(db);
+        if (rc != SQLITE_OK) {
+            *pzErrMsg = sqlite3_mprintf("muninn: failed to register graph_adjacency module");
             return rc;
         }
     }

@@ -86,6 +86,9 @@ GRAPH_SYMBOLS = [
     ("mn_n2v_end", None, [C.c_void_p]),
     ("mn_graph_create", C.c_void_p, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("mn_graph_create_blocked", C.c_void_p, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("mn_graph_from_edges", C.c_void_p, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("mn_graph_export_csr", C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_void_p, C.c_void_p]),
+    ("mn_graph_retain", None, [C.c_void_p]),
     ("mn_graph_destroy", None, [C.c_void_p]),
     ("mn_graph_last_error", C.c_char_p, []),
     ("mn_graph_leiden", C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, _i32p, C.POINTER(C.c_double)]),
@@ -179,6 +182,39 @@ class Graph:
         if not self.h:
             raise MuninnHipError("mn_graph_create_blocked failed: " + _gerr())
         return self
+
+    @classmethod
+    def from_edges(cls, n, src, dst, weights=None, lists="both", device=0):
+        """The graph of an edge list with integer node indices, built on the device (mn_graph_from_edges): out[src] lists
+        dst and in[dst] lists src in row order, as csr_pair_from_edges gives them.  lists: "out", "in" or "both"."""
+        self = cls.__new__(cls)
+        self.L = _glib()
+        self.n = int(n)
+        s, d = np.ascontiguousarray(src, np.int32).reshape(-1), np.ascontiguousarray(dst, np.int32).reshape(-1)
+        if len(s) != len(d):
+            raise ValueError("from_edges: src and dst differ in length")
+        w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+        if w is not None and len(w) != len(s):
+            raise ValueError("from_edges: weights and rows differ in length")
+        self.h = self.L.mn_graph_from_edges(self.n, len(s), s.ctypes.data, d.ctypes.data, None if w is None else w.ctypes.data,
+                                            {"out": 1, "in": 2, "both": 3}[lists], device)
+        if not self.h:
+            raise MuninnHipError("mn_graph_from_edges failed: " + _gerr())
+        return self
+
+    def export_csr(self, which="out"):
+        """One direction as the host's CSR (mn_graph_export_csr) → (off int32[n + 1], tgt int32[E], w float64[E] or None);
+        which: "out" / 0 or "in" / 1.  w is None where the graph holds no weights for that direction."""
+        k = {"out": 0, "in": 1, 0: 0, 1: 1}[which]
+        off = np.zeros(self.n + 1, np.int32)
+        if self.L.mn_graph_export_csr(self.h, k, off, None, None) < 0:
+            raise MuninnHipError(_gerr())
+        e = int(off[-1])
+        tgt, w = np.zeros(e, np.int32), np.zeros(e, np.float64)
+        rc = self.L.mn_graph_export_csr(self.h, k, off, tgt.ctypes.data, w.ctypes.data)
+        if rc < 0:
+            raise MuninnHipError(_gerr())
+        return off, tgt, (w if rc == 1 else None)
 
     def close(self):
         if getattr(self, "h", None):
