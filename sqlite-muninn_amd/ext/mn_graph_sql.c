@@ -2,29 +2,23 @@
  * mn_graph_sql.c — SQL surface of the graph half of the hot path over libmuninn_hip.so:
  *   node2vec_train(edge_table, src_col, dst_col, output_table, dimensions, p, q, num_walks, walk_length,
  *                  window, neg_samples, learning_rate, epochs)          (src/node2vec.c:405-597)
- *   graph_leiden   eponymous table-valued function                      (src/graph_community.c:437-670)
+ *   graph_leiden   eponymous table-valued function, on mn_tvf.h's scaffold (src/graph_community.c:437-670)
  * Same argument lists, defaults, error strings and output rows as the reference.  The SQL ingest
  * (string node ids → first-seen indices, adjacency in edge-table row order) is host C here as it is
  * there — with a hash map instead of the reference's linear scan (src/node2vec.c:72-77) — and the
  * compute is mn_node2vec_train / mn_graph_leiden.
  */
-#include "../../include/muninn_hip.h"
-#include "mn_sqlite_abi.h"
+#include "mn_tvf.h"
 
 #include <stdlib.h>
 #include <string.h>
 
-/* Which device schedule the SQL functions use.  MUNINN_GRAPH_MODE=exact → the reference's sequential
- * semantics (results bit-identical to the reference, latency-bound single wavefront); =fast → the
- * batch-synchronous schedules; unset/auto → exact for small inputs (where the reference's own tests
- * live), fast beyond.   */
+/* Which device schedule the SQL functions use: MUNINN_GRAPH_MODE (mn_env_graph_mode) forces the reference's sequential
+ * semantics (results bit-identical to the reference, latency-bound single wavefront) or the batch-synchronous schedules;
+ * auto → exact for small inputs (where the reference's own tests live), fast beyond.   */
 static int graph_mode_fast(long long work, long long small_limit) {
-    const char *e = getenv("MUNINN_GRAPH_MODE");
-    if (e && !strcmp(e, "exact"))
-        return 0;
-    if (e && !strcmp(e, "fast"))
-        return 1;
-    return work > small_limit;
+    const int mode = mn_env_graph_mode();
+    return mode == MN_GRAPH_MODE_AUTO ? work > small_limit : mode == MN_GRAPH_MODE_FAST;
 }
 
 #include "mn_nodemap.h" /* identifiers, string → first-seen index map */
@@ -245,98 +239,8 @@ static void fn_node2vec_train(sqlite3_context *ctx, int argc, sqlite3_value **ar
 
 /* ───────────────────────── graph_leiden ───────────────────────── */
 
-typedef struct {
-    sqlite3_vtab base;
-    sqlite3 *db;
-} LeiVtab;
-
-typedef struct {
-    sqlite3_vtab_cursor base;
-    char **node;
-    int *community;
-    double Q;
-    int n, pos, eof;
-} LeiCursor;
-
-enum { LC_NODE = 0, LC_COMM, LC_MOD, LC_EDGE_TABLE, LC_SRC, LC_DST, LC_WEIGHT, LC_RES, LC_DIR, LC_TS, LC_T0, LC_T1 };
-
-static int lei_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    (void)aux; (void)argc; (void)argv; (void)err;
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(  node TEXT, community_id INTEGER, modularity REAL,"
-                                      "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
-                                      "  weight_col TEXT HIDDEN, resolution REAL HIDDEN,"
-                                      "  direction TEXT HIDDEN, timestamp_col TEXT HIDDEN,"
-                                      "  time_start HIDDEN, time_end HIDDEN)");
-    if (rc != SQLITE_OK)
-        return rc;
-    LeiVtab *v = (LeiVtab *)sqlite3_malloc((int)sizeof(LeiVtab));
-    if (!v)
-        return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-
-static int lei_disconnect(sqlite3_vtab *v) {
-    sqlite3_free(v);
-    return SQLITE_OK;
-}
-
-/* graph_best_index_common (src/graph_common.h:62-96): hidden columns → bitmask idxNum, argv in column order */
-static int lei_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
-    (void)v;
-    int which[9];
-    for (int j = 0; j < 9; j++)
-        which[j] = -1;
-    for (int i = 0; i < ii->nConstraint; i++) {
-        if (!ii->aConstraint[i].usable || ii->aConstraint[i].op != SQLITE_INDEX_CONSTRAINT_EQ)
-            continue;
-        int col = ii->aConstraint[i].iColumn;
-        if (col >= LC_EDGE_TABLE && col <= LC_T1)
-            which[col - LC_EDGE_TABLE] = i;
-    }
-    int arg = 1, mask = 0;
-    for (int j = 0; j < 9; j++)
-        if (which[j] >= 0) {
-            ii->aConstraintUsage[which[j]].argvIndex = arg++;
-            ii->aConstraintUsage[which[j]].omit = 1;
-            mask |= 1 << j;
-        }
-    ii->idxNum = mask;
-    ii->estimatedCost = (mask & 0x7) == 0x7 ? 5000.0 : 1e12;
-    return SQLITE_OK;
-}
-
-static int lei_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
-    (void)v;
-    LeiCursor *c = (LeiCursor *)calloc(1, sizeof(LeiCursor));
-    if (!c)
-        return SQLITE_NOMEM;
-    c->eof = 1;
-    *out = &c->base;
-    return SQLITE_OK;
-}
-
-static void lei_clear(LeiCursor *c) {
-    for (int i = 0; i < c->n; i++)
-        free(c->node[i]);
-    free(c->node);
-    free(c->community);
-    c->node = 0;
-    c->community = 0;
-    c->n = 0;
-}
-
-static int lei_close(sqlite3_vtab_cursor *cur) {
-    lei_clear((LeiCursor *)cur);
-    free(cur);
-    return SQLITE_OK;
-}
-
-static const char *safe_text(sqlite3_value *v) {
-    return v && sqlite3_value_type(v) != SQLITE_NULL ? (const char *)sqlite3_value_text(v) : 0;
-}
+/* hidden columns by position (mn_tvf_args), after node, community_id, modularity */
+enum { LH_EDGE_TABLE = 0, LH_SRC, LH_DST, LH_WEIGHT, LH_RES, LH_DIR, LH_TS, LH_T0, LH_T1, LH_COUNT };
 
 /* ── a graph_adjacency table as edge_table (src/graph_community.c:577-581) ──
  * The reference recognises one by the 'edge_table' key in "{t}_config" (is_graph_adjacency,
@@ -463,32 +367,11 @@ static mn_graph *adj_load_fresh(sqlite3 *db, const char *t, char ***ids_out, int
     return g;
 }
 
-/* run_leiden on a device graph and hand the result to the cursor (takes ownership of ids) */
-static int lei_run(LeiCursor *c, LeiVtab *vt, mn_graph *g, int n, char **ids, const char *direction, double resolution) {
-    c->community = (int *)malloc((size_t)n * sizeof(int));
-    int rc = mn_graph_leiden(g, resolution, !strcmp(direction, "both"),
-                             graph_mode_fast(n, 2000) ? MN_LEIDEN_BATCHED : MN_LEIDEN_SEQUENTIAL, 0, c->community, &c->Q);
-    mn_graph_destroy(g);
-    if (rc != 0) {
-        vt->base.zErrMsg = sqlite3_mprintf("graph_leiden: %s", mn_graph_last_error());
-        for (int i = 0; i < n; i++)
-            free(ids[i]);
-        free(ids);
-        free(c->community);
-        c->community = 0;
-        return SQLITE_ERROR;
-    }
-    c->node = ids;
-    c->n = n;
-    c->eof = 0;
-    return SQLITE_OK;
-}
-
 /* graph_data_load (src/graph_load.c:144-250) — or, when edge_table names a graph_adjacency table, graph_data_load_from_adjacency
  * (src/graph_adjacency.c:1532-1573) — straight to a device graph: text ids → first-seen indices, out / in lists in row order
  * for the directions loaded, weights when a weight column is given.  SQLITE_OK with *g_out = NULL for an empty graph; on error
- * *err is set (sqlite3_mprintf).  The ids (malloc'ed strings) and the graph belong to the caller.  Shared by graph_leiden and
- * the centrality TVFs (mn_graph_tvf.c). */
+ * *err is set (sqlite3_mprintf).  The ids (malloc'ed strings) and the graph belong to the caller.  Declared in mn_tvf.h: every
+ * table-valued function that works on a device graph loads it here. */
 int mn_sql_load_graph(sqlite3 *db, const char *who, const char *edge_table, const char *src_col, const char *dst_col,
                       const char *weight_col, const char *direction, const char *ts_col, sqlite3_value *t0, sqlite3_value *t1,
                       mn_graph **g_out, char ***ids_out, int *n_out, char **err) {
@@ -654,86 +537,61 @@ int mn_sql_load_graph(sqlite3 *db, const char *who, const char *edge_table, cons
 }
 
 /* src/graph_community.c:516-610 + graph_data_load (src/graph_load.c:144-250) */
-static int lei_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
-    (void)idxStr;
-    LeiCursor *c = (LeiCursor *)cur;
-    LeiVtab *vt = (LeiVtab *)cur->pVtab;
-    lei_clear(c);
-    c->pos = 0;
-    c->eof = 1;
+static int lei_filter(MnTvfCursor *c, int idxNum, int argc, sqlite3_value **argv) {
+    MnTvfVtab *vt = mn_tvf_vtab(c);
     if (argc < 3)
         return SQLITE_OK;
-    const char *edge_table = 0, *src_col = 0, *dst_col = 0, *weight_col = 0, *direction = 0, *ts_col = 0;
-    sqlite3_value *t0 = 0, *t1 = 0;
-    double resolution = 1.0;
-    int pos = 0;
-    for (int bit = 0; bit < 9 && pos < argc; bit++) {
-        if (!(idxNum & (1 << bit)))
-            continue;
-        switch (bit + LC_EDGE_TABLE) {
-        case LC_EDGE_TABLE: edge_table = safe_text(argv[pos]); break;
-        case LC_SRC: src_col = safe_text(argv[pos]); break;
-        case LC_DST: dst_col = safe_text(argv[pos]); break;
-        case LC_WEIGHT: weight_col = safe_text(argv[pos]); break;
-        case LC_RES: resolution = sqlite3_value_double(argv[pos]); break;
-        case LC_DIR: direction = safe_text(argv[pos]); break;
-        case LC_TS: ts_col = safe_text(argv[pos]); break;
-        case LC_T0: t0 = argv[pos]; break;
-        case LC_T1: t1 = argv[pos]; break;
-        }
-        pos++;
-    }
+    sqlite3_value *v[MN_TVF_MAX_HIDDEN];
+    mn_tvf_args(vt->def, idxNum, argc, argv, v);
+    const double resolution = v[LH_RES] ? sqlite3_value_double(v[LH_RES]) : 1.0;
+    const char *direction = mn_value_text(v[LH_DIR]);
     if (!direction)
         direction = "both";
     mn_graph *g = 0;
-    char **ids = 0, *err = 0;
-    int n = 0;
-    if (mn_sql_load_graph(vt->db, "graph_leiden", edge_table, src_col, dst_col, weight_col, direction, ts_col, t0, t1, &g, &ids, &n,
+    char *err = 0;
+    if (mn_sql_load_graph(vt->db, "graph_leiden", mn_value_text(v[LH_EDGE_TABLE]), mn_value_text(v[LH_SRC]), mn_value_text(v[LH_DST]),
+                          mn_value_text(v[LH_WEIGHT]), direction, mn_value_text(v[LH_TS]), v[LH_T0], v[LH_T1], &g, &c->ids, &c->n_ids,
                           &err) != SQLITE_OK) {
-        vt->base.zErrMsg = err;
+        vt->base.zErrMsg = err; /* passed through as it is */
         return SQLITE_ERROR;
     }
     if (!g)
         return SQLITE_OK; /* empty graph */
-    return lei_run(c, vt, g, n, ids, direction, resolution); /* ownership of the ids moves to the cursor */
-}
-
-static int lei_next(sqlite3_vtab_cursor *cur) {
-    LeiCursor *c = (LeiCursor *)cur;
-    c->pos++;
-    c->eof = c->pos >= c->n;
+    const int n = c->n_ids;
+    int *community = (int *)mn_tvf_alloc(c, 0, n, sizeof(int));
+    int rc = community ? mn_graph_leiden(g, resolution, !strcmp(direction, "both"),
+                                         graph_mode_fast(n, 2000) ? MN_LEIDEN_BATCHED : MN_LEIDEN_SEQUENTIAL, 0, community, &c->q)
+                       : 0;
+    mn_graph_destroy(g);
+    if (!community)
+        return SQLITE_NOMEM;
+    if (rc != 0) {
+        vt->base.zErrMsg = sqlite3_mprintf("graph_leiden: %s", mn_graph_last_error());
+        return SQLITE_ERROR;
+    }
+    c->n = n;
+    c->eof = 0;
     return SQLITE_OK;
 }
-static int lei_eof(sqlite3_vtab_cursor *cur) { return ((LeiCursor *)cur)->eof; }
-static int lei_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
-    LeiCursor *c = (LeiCursor *)cur;
+
+static void lei_column(const MnTvfCursor *c, sqlite3_context *ctx, int col) {
     switch (col) {
-    case LC_NODE: sqlite3_result_text(ctx, c->node[c->pos], -1, SQLITE_TRANSIENT); break;
-    case LC_COMM: sqlite3_result_int(ctx, c->community[c->pos]); break;
-    case LC_MOD: sqlite3_result_double(ctx, c->Q); break;
+    case 0: sqlite3_result_text(ctx, c->ids[c->pos], -1, SQLITE_TRANSIENT); break;
+    case 1: sqlite3_result_int(ctx, ((const int *)c->buf[0])[c->pos]); break;
+    case 2: sqlite3_result_double(ctx, c->q); break;
     default: sqlite3_result_null(ctx); break;
     }
-    return SQLITE_OK;
-}
-static int lei_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
-    *out = ((LeiCursor *)cur)->pos;
-    return SQLITE_OK;
 }
 
-static sqlite3_module leiden_module = {
-    .iVersion = 0,
-    .xCreate = 0, /* eponymous */
-    .xConnect = lei_connect,
-    .xBestIndex = lei_best_index,
-    .xDisconnect = lei_disconnect,
-    .xDestroy = lei_disconnect,
-    .xOpen = lei_open,
-    .xClose = lei_close,
-    .xFilter = lei_filter,
-    .xNext = lei_next,
-    .xEof = lei_eof,
-    .xColumn = lei_column,
-    .xRowid = lei_rowid,
+static const MnTvf leiden_tvf = {
+    .name = "graph_leiden",
+    .schema = "CREATE TABLE x(  node TEXT, community_id INTEGER, modularity REAL,"
+              "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
+              "  weight_col TEXT HIDDEN, resolution REAL HIDDEN,"
+              "  direction TEXT HIDDEN, timestamp_col TEXT HIDDEN,"
+              "  time_start HIDDEN, time_end HIDDEN)",
+    .first_hidden = 3, .n_hidden = LH_COUNT, .rule = MN_TVF_COMPACTED, .required_mask = 0x7, .cost = 5000.0,
+    .filter = lei_filter, .column = lei_column,
 };
 
 /* one registration per reference registration function, so that an integrated build can keep the reference's
@@ -742,7 +600,7 @@ int mn_register_node2vec(sqlite3 *db) { /* node2vec_register_functions, src/node
     return sqlite3_create_function(db, "node2vec_train", 13, SQLITE_UTF8 | SQLITE_DETERMINISTIC, 0, fn_node2vec_train, 0, 0);
 }
 int mn_register_leiden(sqlite3 *db) { /* community_register_tvfs, src/graph_community.c:668-670 */
-    return sqlite3_create_module(db, "graph_leiden", &leiden_module, 0);
+    return mn_tvf_register(db, &leiden_tvf);
 }
 int mn_register_graph_functions(sqlite3 *db) {
     int rc = mn_register_node2vec(db);

@@ -1,5 +1,5 @@
 /*
- * mn_traverse_tvf.c — graph_bfs over libmuninn_hip.so.
+ * mn_traverse_tvf.c — graph_bfs over libmuninn_hip.so: its descriptor, xFilter and xColumn on the scaffold of mn_tvf.h.
  * Same eponymous table-valued function as the reference (src/graph_tvf.c:759-967 over run_bfs, :230-309): declared schema,
  * xBestIndex handing the hidden-column constraints over in the order SQLite lists them, xFilter mapping them BY POSITION
  * (:876-887 — so `direction='both'` without `max_depth` lands in max_depth, reads as 0 and answers the start row), defaults
@@ -10,133 +10,21 @@
  * A translation unit of its own: the integrated build (oracle/Makefile) links the reference's graph_tvf.c, which registers
  * its own graph_bfs, next to this repository's other extension sources — nothing of theirs refers to this file.
  */
-#include "../../include/muninn_hip.h"
-#include "mn_sqlite_abi.h"
+#include "mn_tvf.h"
 
 #include "mn_nodemap.h"
 
-int mn_sql_load_graph(sqlite3 *db, const char *who, const char *edge_table, const char *src_col, const char *dst_col,
-                      const char *weight_col, const char *direction, const char *ts_col, sqlite3_value *t0, sqlite3_value *t1,
-                      mn_graph **g_out, char ***ids_out, int *n_out, char **err); /* mn_graph_sql.c */
-
-typedef struct {
-    sqlite3_vtab base;
-    sqlite3 *db;
-} BfsVtab;
-
-typedef struct {
-    sqlite3_vtab_cursor base;
-    char **ids; /* node ids, first-seen order (owned) */
-    int n_ids;
-    char *start; /* the start node's text when it is the only row (owned) */
-    int *node, *depth, *parent;
-    long long n, pos;
-    int eof;
-} BfsCursor;
-
-enum { GB_NODE = 0, GB_DEPTH, GB_PARENT, GB_EDGE_TABLE, GB_SRC, GB_DST, GB_START, GB_MAX_DEPTH, GB_DIRECTION };
-
-static void gb_clear(BfsCursor *c) {
-    for (int i = 0; i < c->n_ids; i++)
-        free(c->ids[i]);
-    free(c->ids);
-    free(c->start);
-    free(c->node);
-    free(c->depth);
-    free(c->parent);
-    c->ids = 0;
-    c->start = 0;
-    c->node = c->depth = c->parent = 0;
-    c->n_ids = 0;
-    c->n = c->pos = 0;
-    c->eof = 1;
-}
-
-static int gb_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    (void)aux; (void)argc; (void)argv; (void)err;
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x("
-                                      "  node TEXT, depth INTEGER, parent TEXT,"
-                                      "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
-                                      "  start_node TEXT HIDDEN, max_depth INTEGER HIDDEN, direction TEXT HIDDEN"
-                                      ")");
-    if (rc != SQLITE_OK)
-        return rc;
-    BfsVtab *v = (BfsVtab *)sqlite3_malloc((int)sizeof(BfsVtab));
-    if (!v)
-        return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-
-static int gb_disconnect(sqlite3_vtab *v) {
-    sqlite3_free(v);
-    return SQLITE_OK;
-}
-
-/* gtrav_best_index (:822-838): argvIndex counts up in the order SQLite lists the constraints, whatever the column */
-static int gb_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
-    (void)v;
-    int arg = 1;
-    for (int i = 0; i < ii->nConstraint; i++) {
-        if (!ii->aConstraint[i].usable)
-            continue;
-        int col = ii->aConstraint[i].iColumn;
-        if (col >= GB_EDGE_TABLE && col <= GB_DIRECTION && ii->aConstraint[i].op == SQLITE_INDEX_CONSTRAINT_EQ) {
-            ii->aConstraintUsage[i].argvIndex = arg++;
-            ii->aConstraintUsage[i].omit = 1;
-        }
-    }
-    ii->estimatedCost = 1000.0;
-    return SQLITE_OK;
-}
-
-static int gb_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
-    (void)v;
-    BfsCursor *c = (BfsCursor *)calloc(1, sizeof(BfsCursor));
-    if (!c)
-        return SQLITE_NOMEM;
-    c->eof = 1;
-    *out = &c->base;
-    return SQLITE_OK;
-}
-
-static int gb_close(sqlite3_vtab_cursor *cur) {
-    gb_clear((BfsCursor *)cur);
-    free(cur);
-    return SQLITE_OK;
-}
+enum { GB_NODE = 0, GB_DEPTH, GB_PARENT, GB_EDGE_TABLE }; /* columns; the result slots are node, depth, parent */
 
 /* whether "SELECT a FROM t WHERE b = ?" compiles: what run_bfs prepares for a direction it follows (:250-265) */
 static int gb_columns_exist(sqlite3 *db, const char *t, const char *a, const char *b) {
-    char *sql = sqlite3_mprintf("SELECT \"%w\" FROM \"%w\" WHERE \"%w\" = ?", a, t, b);
-    if (!sql)
-        return 0;
-    sqlite3_stmt *st = 0;
-    int rc = sqlite3_prepare_v2(db, sql, -1, &st, 0);
-    sqlite3_free(sql);
-    sqlite3_finalize(st);
-    return rc == SQLITE_OK;
+    return mn_sql_compiles(db, "SELECT \"%w\" FROM \"%w\" WHERE \"%w\" = ?", a, t, b);
 }
 
-static int gb_start_only(BfsCursor *c, const char *start) {
-    size_t len = strlen(start) + 1;
-    c->start = (char *)malloc(len);
-    if (!c->start)
-        return SQLITE_NOMEM;
-    memcpy(c->start, start, len);
-    c->n = 1;
-    c->eof = 0;
-    return SQLITE_OK;
-}
-
-static int gb_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
-    (void)idxNum; (void)idxStr;
-    BfsCursor *c = (BfsCursor *)cur;
-    BfsVtab *vt = (BfsVtab *)cur->pVtab;
+static int gb_filter(MnTvfCursor *c, int idxNum, int argc, sqlite3_value **argv) {
+    (void)idxNum;
+    MnTvfVtab *vt = mn_tvf_vtab(c);
     static const char *failed = "graph_bfs: traversal failed (check table/column names exist)";
-    gb_clear(c);
     const char *edge_table = 0, *src_col = 0, *dst_col = 0, *start = 0, *direction = "forward";
     int max_depth = 100;
     if (argc >= 1) edge_table = (const char *)sqlite3_value_text(argv[0]); /* by position (:876-887) */
@@ -169,17 +57,16 @@ static int gb_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, i
         return SQLITE_ERROR;
     }
     if (max_depth <= 0 || (!go_forward && !go_reverse)) /* the start node is popped and not expanded (:280-282) */
-        return gb_start_only(c, start);
+        return mn_tvf_lone_row(c, start);
     mn_graph *g = 0;
     char *err = 0;
-    int n = 0;
-    if (mn_sql_load_graph(vt->db, "graph_bfs", edge_table, src_col, dst_col, 0, direction, 0, 0, 0, &g, &c->ids, &n, &err) !=
-        SQLITE_OK) {
+    if (mn_sql_load_graph(vt->db, "graph_bfs", edge_table, src_col, dst_col, 0, direction, 0, 0, 0, &g, &c->ids, &c->n_ids, &err) !=
+        SQLITE_OK) { /* whatever it says is replaced */
         sqlite3_free(err);
         vt->base.zErrMsg = sqlite3_mprintf("%s", failed);
         return SQLITE_ERROR;
     }
-    c->n_ids = n;
+    const int n = c->n_ids;
     int seed = -1;
     for (int i = 0; g && i < n; i++)
         if (!strcmp(c->ids[i], start)) {
@@ -189,21 +76,19 @@ static int gb_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, i
     if (seed < 0) { /* an empty table, or no row names the start node */
         if (g)
             mn_graph_destroy(g);
-        return gb_start_only(c, start);
+        return mn_tvf_lone_row(c, start);
     }
-    const int dir = go_forward && go_reverse ? 0 : go_reverse ? 2 : 1;
     int64_t row_off[2] = {0, 0};
-    const int64_t rows = mn_graph_bfs(g, dir, 1, &seed, max_depth, row_off, 0);
+    const int64_t rows = mn_graph_bfs(g, mn_dir_code(direction), 1, &seed, max_depth, row_off, 0);
     int rc = rows < 0 ? SQLITE_ERROR : SQLITE_OK;
     if (rc == SQLITE_OK) {
-        c->node = (int *)malloc((size_t)rows * sizeof(int));
-        c->depth = (int *)malloc((size_t)rows * sizeof(int));
-        c->parent = (int *)malloc((size_t)rows * sizeof(int));
-        if (!c->node || !c->depth || !c->parent) {
+        int *node = (int *)mn_tvf_alloc(c, GB_NODE, rows, sizeof(int)), *depth = (int *)mn_tvf_alloc(c, GB_DEPTH, rows, sizeof(int));
+        int *parent = (int *)mn_tvf_alloc(c, GB_PARENT, rows, sizeof(int));
+        if (!node || !depth || !parent) {
             mn_graph_destroy(g);
             return SQLITE_NOMEM;
         }
-        rc = mn_graph_bfs_rows(g, c->node, c->depth, c->parent) == 0 ? SQLITE_OK : SQLITE_ERROR;
+        rc = mn_graph_bfs_rows(g, node, depth, parent) == 0 ? SQLITE_OK : SQLITE_ERROR;
     }
     if (rc != SQLITE_OK)
         vt->base.zErrMsg = sqlite3_mprintf("graph_bfs: %s", mn_graph_last_error());
@@ -215,46 +100,39 @@ static int gb_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, i
     return SQLITE_OK;
 }
 
-static int gb_next(sqlite3_vtab_cursor *cur) {
-    BfsCursor *c = (BfsCursor *)cur;
-    c->pos++;
-    c->eof = c->pos >= c->n;
-    return SQLITE_OK;
-}
-static int gb_eof(sqlite3_vtab_cursor *cur) { return ((BfsCursor *)cur)->eof; }
-static int gb_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
-    *out = ((BfsCursor *)cur)->pos;
-    return SQLITE_OK;
-}
-
-static int gb_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
-    BfsCursor *c = (BfsCursor *)cur;
+static void gb_column(const MnTvfCursor *c, sqlite3_context *ctx, int col) {
+    const int *const node = (const int *)c->buf[GB_NODE], *const depth = (const int *)c->buf[GB_DEPTH];
+    const int *const parent = (const int *)c->buf[GB_PARENT];
     switch (col) {
     case GB_NODE:
-        sqlite3_result_text(ctx, c->start ? c->start : c->ids[c->node[c->pos]], -1, SQLITE_TRANSIENT);
+        sqlite3_result_text(ctx, c->lone ? c->lone : c->ids[node[c->pos]], -1, SQLITE_TRANSIENT);
         break;
     case GB_DEPTH:
-        sqlite3_result_int(ctx, c->start ? 0 : c->depth[c->pos]);
+        sqlite3_result_int(ctx, c->lone ? 0 : depth[c->pos]);
         break;
     case GB_PARENT:
-        if (c->start || c->parent[c->pos] < 0)
+        if (c->lone || parent[c->pos] < 0)
             sqlite3_result_null(ctx);
         else
-            sqlite3_result_text(ctx, c->ids[c->parent[c->pos]], -1, SQLITE_TRANSIENT);
+            sqlite3_result_text(ctx, c->ids[parent[c->pos]], -1, SQLITE_TRANSIENT);
         break;
     default:
         sqlite3_result_null(ctx);
         break;
     }
-    return SQLITE_OK;
 }
 
-static sqlite3_module bfs_module = {
-    .iVersion = 0, .xCreate = 0, .xConnect = gb_connect, .xBestIndex = gb_best_index, .xDisconnect = gb_disconnect,
-    .xDestroy = gb_disconnect, .xOpen = gb_open, .xClose = gb_close, .xFilter = gb_filter, .xNext = gb_next,
-    .xEof = gb_eof, .xColumn = gb_column, .xRowid = gb_rowid,
+static const MnTvf bfs_tvf = {
+    .name = "graph_bfs",
+    .schema = "CREATE TABLE x("
+              "  node TEXT, depth INTEGER, parent TEXT,"
+              "  edge_table TEXT HIDDEN, src_col TEXT HIDDEN, dst_col TEXT HIDDEN,"
+              "  start_node TEXT HIDDEN, max_depth INTEGER HIDDEN, direction TEXT HIDDEN"
+              ")",
+    .first_hidden = GB_EDGE_TABLE, .n_hidden = 6, .rule = MN_TVF_IN_LISTED_ORDER, .required_mask = 0, .cost = 1000.0, /* gtrav_best_index (:822-838) */
+    .filter = gb_filter, .column = gb_column,
 };
 
 int mn_register_traversal_tvfs(sqlite3 *db) { /* the first of graph_register_tvfs (src/graph_tvf.c:1898-1914) */
-    return sqlite3_create_module(db, "graph_bfs", &bfs_module, 0);
+    return mn_tvf_register(db, &bfs_tvf);
 }
