@@ -439,6 +439,35 @@ int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, const int *see
  * parent (-1 for a seed) of each, row count as returned; any pointer may be NULL.  0 / -1. */
 int mn_graph_bfs_rows(mn_graph *g, int *node, int *depth, int *parent);
 
+typedef struct {
+    int64_t rows, chunks, entries_scanned, max_frames; /* max_frames: most frames any seed's stack held at once */
+    double device_ms;
+} mn_dfs_stats;
+/* run_dfs (src/graph_tvf.c:322-416) for n_seeds start nodes at once: per seed the rows (node, depth, parent) in the order the
+ * reference's stack pops them.  The reference pushes every neighbour that is not visited at that moment (out-list, then
+ * in-list, each in table-row order) as an item (node, depth + 1, parent) and drops a popped item whose node is visited, so the
+ * last-listed neighbour goes first, a node's depth is that of the item popped first (not its BFS depth), and a node first
+ * reached at max_depth is marked, not expanded (:383), and blocks any later, shallower way to it.  The device runs the frame
+ * form of the same procedure (csrc/mn_dfs.hip): one frame (u, cursor) per node being expanded, the frame's
+ * index its depth, the cursor running from deg(u) down to 0 over out-list ‖ in-list; a step takes the entry below the
+ * cursor, and if its node v is not visited marks it, emits (v, depth + 1, u) and, while depth + 1 < max_depth, pushes
+ * (v, deg(v)); a frame whose cursor is 0 is popped.  One wavefront per seed reads 64 entries per step.  Conventions of
+ * mn_graph_bfs: direction 0 = both, 1 = forward, 2 = reverse and the same requirement on which lists the graph holds; seeds
+ * may repeat, each gets its own answer; n_seeds == 0 answers 0 rows; max_depth <= 0 answers the seed rows without a launch;
+ * weights are ignored; row_off[n_seeds + 1]: seed i's rows are row_off[i] .. row_off[i + 1] - 1 of mn_graph_dfs_rows, parent
+ * -1 for a seed's own row.  Seeds go through in chunks under a scratch budget: half of the free device memory, or
+ * MN_DFS_SCRATCH_MB MiB (fractions allowed) — per seed of a chunk 12 bytes per node (its rows) + 4 bytes per 32 nodes (its
+ * visited bitmap, cleared per chunk) + 8 bytes per frame, min(n, max_depth) frames; at least one seed; the scratch stays with
+ * the handle until mn_graph_destroy.  A seed outside 0 .. n - 1, n_seeds < 0, a missing list, n > 2^26 or 2^31 or more list
+ * entries in the lists followed is an error before any launch.  Every seed's step count is bounded on the device by (list
+ * entries followed) + 2 n + 2; an overrun is reported as an internal error.  stats may be NULL.  Sets mn_graph_last_ms.
+ * Returns the row count, or -1 with mn_graph_last_error set. */
+int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, const int *seeds, int max_depth, int64_t *row_off,
+                     mn_dfs_stats *stats);
+/* The rows of the last mn_graph_dfs on this handle (they stay with it until the next mn_graph_dfs or mn_graph_destroy, and are
+ * independent of mn_graph_bfs's): node, depth and parent (-1 for a seed) of each; any pointer may be NULL.  0 / -1. */
+int mn_graph_dfs_rows(mn_graph *g, int *node, int *depth, int *parent);
+
 /* ---- graph_shortest_path (src/graph_tvf.c:472-753) ---- */
 typedef enum {
     MN_SP_AUTO = 0,      /* replay when the graph holds a negative weight or E_out + 1 <= MN_SP_REPLAY_MAX (4096), else fast */

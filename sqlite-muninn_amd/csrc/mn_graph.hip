@@ -1,5 +1,5 @@
 // mn_graph.hip — the mn_graph handle: device-resident CSR adjacency (src/graph_csr.h:27-34) uploaded once and shared by
-// the algorithms over it (mn_leiden.hip + mn_leiden_eval.hpp, mn_centrality.hip, mn_bfs.hip, mn_select.hip, mn_sssp.hip), and their common error string.
+// the algorithms over it (mn_leiden.hip + mn_leiden_eval.hpp, mn_centrality.hip, mn_bfs.hip, mn_dfs.hip, mn_select.hip, mn_sssp.hip), and their common error string.
 // Host code only.
 #include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
@@ -192,6 +192,8 @@ extern "C" void mn_graph_destroy(mn_graph *g) {
         lei_work_free(g->work);
     if (g->bfs)
         bfs_work_free(g->bfs);
+    if (g->dfs)
+        dfs_work_free(g->dfs);
     if (g->sel)
         sel_work_free(g->sel);
     if (g->sp)

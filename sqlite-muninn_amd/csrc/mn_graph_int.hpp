@@ -1,7 +1,7 @@
 // mn_graph_int.hpp — what the translation units behind the mn_graph handle share: mn_graph.hip (handle, CSR upload),
 // mn_csr_build.hip (the handle built on the device from an edge list),
 // mn_leiden.hip (with mn_leiden_eval.hpp, the device code of its evaluation, included by it alone), mn_centrality.hip and
-// mn_bfs.hip, mn_select.hip and mn_sssp.hip.  Host declarations and the kernels' view of the CSR only: device code does not cross a translation unit, every
+// mn_bfs.hip, mn_dfs.hip, mn_select.hip and mn_sssp.hip.  Host declarations and the kernels' view of the CSR only: device code does not cross a translation unit, every
 // kernel lives in the file that launches it.
 #pragma once
 #include "../../include/muninn_hip.h"
@@ -23,6 +23,7 @@ struct DevGraph {
 
 struct LeiWork; // mn_leiden.hip
 struct BfsWork; // mn_bfs.hip
+struct DfsWork; // mn_dfs.hip
 struct SelWork; // mn_select.hip
 struct SpWork;  // mn_sssp.hip
 
@@ -42,6 +43,7 @@ struct mn_graph {
     std::vector<int> h_off_out, h_off_in; // host copies of the offsets (degrees: list of wide nodes, scratch sizing)
     struct LeiWork *work = nullptr;       // run_leiden's device buffers, allocated on first use and kept
     struct BfsWork *bfs = nullptr;        // mn_graph_bfs's scratch and the rows of its last call, likewise
+    struct DfsWork *dfs = nullptr;        // mn_graph_dfs's, likewise
     struct SelWork *sel = nullptr;        // mn_graph_select's, likewise
     struct SpWork *sp = nullptr;          // mn_graph_shortest_paths's weight summary and the rows of its last call
 };
@@ -74,5 +76,6 @@ inline size_t scratch_budget(const char *env, size_t reserve) {
 
 void lei_work_free(LeiWork *w); // mn_leiden.hip: releases and deletes a graph's Leiden workspace (mn_graph_destroy)
 void bfs_work_free(BfsWork *w); // mn_bfs.hip: the same for the traversal's
+void dfs_work_free(DfsWork *w); // mn_dfs.hip: the same for the depth-first traversal's
 void sel_work_free(SelWork *w); // mn_select.hip: the same for the selectors'
 void sp_work_free(SpWork *w);   // mn_sssp.hip: the same for the shortest paths'

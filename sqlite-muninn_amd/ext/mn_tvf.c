@@ -1,6 +1,6 @@
 /*
  * mn_tvf.c — the one sqlite3_module behind graph_components, graph_pagerank, graph_node_betweenness, graph_edge_betweenness,
- * graph_closeness, graph_degree, graph_leiden, graph_bfs, graph_shortest_path and graph_select (mn_tvf.h).  The descriptor
+ * graph_closeness, graph_degree, graph_leiden, graph_bfs, graph_dfs, graph_shortest_path and graph_select (mn_tvf.h).  The descriptor
  * travels as the module's pAux; the entry points below read it and never ask which function they serve.
  */
 #include "mn_tvf.h"

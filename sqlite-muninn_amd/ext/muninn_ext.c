@@ -6,7 +6,7 @@
  * the first failure aborts with *pzErrMsg set via sqlite3_mprintf.  Registered here: the
  * hot-path surface of SURVEY §8(b) — `hnsw_index` (+ `hnsw0` alias), `node2vec_train`,
  * `graph_leiden` — and §8 f-4's `graph_components` / `graph_pagerank` / `graph_node_betweenness` / `graph_edge_betweenness` /
- * `graph_degree` / `graph_closeness` (all on the scaffold of mn_tvf.h), the reference's `graph_bfs` (src/graph_tvf.c:230-309; mn_traverse_tvf.c), its
+ * `graph_degree` / `graph_closeness` (all on the scaffold of mn_tvf.h), the reference's `graph_bfs` and `graph_dfs` (src/graph_tvf.c:230-416; mn_traverse_tvf.c), its
  * `graph_shortest_path` (src/graph_tvf.c:472-753; mn_path_tvf.c), its `graph_select` (src/graph_select_tvf.c;
  * mn_select_tvf.c), its `muninn_extract_er` (src/llama_er.c) and its `graph_adjacency` virtual table (src/graph_adjacency.c;
  * mn_adjacency_vtab.c), each backed by libmuninn_hip.so (include/muninn_hip.h).

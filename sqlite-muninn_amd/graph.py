@@ -23,6 +23,11 @@ class BfsStats(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class DfsStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("chunks", C.c_int64), ("entries_scanned", C.c_int64), ("max_frames", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 class SpStats(C.Structure):
     _fields_ = [("mode_used", C.c_int), ("chunks", C.c_int), ("sources", C.c_int), ("pops", C.c_int64), ("pushes", C.c_int64),
                 ("relaxations", C.c_int64), ("passes", C.c_int64), ("device_ms", C.c_double)]
@@ -104,6 +109,9 @@ GRAPH_SYMBOLS = [
     ("mn_graph_bfs", C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
                                  np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(BfsStats)]),
     ("mn_graph_bfs_rows", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
+    ("mn_graph_dfs", C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                 np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(DfsStats)]),
+    ("mn_graph_dfs_rows", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
     ("mn_graph_shortest_paths", C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                             np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(SpStats)]),
     ("mn_graph_shortest_paths_rows", C.c_int, [C.c_void_p, _i32p, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]),
@@ -268,6 +276,28 @@ class Graph:
     def bfs(self, seed, max_depth=100, direction="forward"):
         """graph_bfs's rows from one start node → (node, depth, parent) int32 arrays; self.bfs_stats as for bfs_batch"""
         return self.bfs_batch([seed], max_depth, direction)[1:]
+
+    def dfs_batch(self, seeds, max_depth=100, direction="forward"):
+        """run_dfs (src/graph_tvf.c:322-416) from every seed at once → (row_off[len(seeds) + 1] int64, node, depth, parent
+        int32): seed i's rows, in the reference's pop order, are row_off[i] .. row_off[i + 1] - 1; parent is -1 for a seed's
+        own row.  One wavefront per seed (csrc/mn_dfs.hip).  The call's statistics are in self.dfs_stats afterwards."""
+        seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+        row_off = np.zeros(len(seeds) + 1, np.int64)
+        st = DfsStats()
+        d = {"both": 0, "forward": 1, "reverse": 2}[direction]
+        rows = self.L.mn_graph_dfs(self.h, d, len(seeds), seeds.ctypes.data if len(seeds) else None, int(max_depth), row_off,
+                                   C.byref(st))
+        if rows < 0:
+            raise MuninnHipError(_gerr())
+        out = [np.empty(max(rows, 1), np.int32) for _ in range(3)]
+        if self.L.mn_graph_dfs_rows(self.h, *out) != 0:
+            raise MuninnHipError(_gerr())
+        self.dfs_stats = {n: getattr(st, n) for n, _ in DfsStats._fields_}
+        return (row_off,) + tuple(a[:rows] for a in out)
+
+    def dfs(self, seed, max_depth=100, direction="forward"):
+        """graph_dfs's rows from one start node → (node, depth, parent) int32 arrays; self.dfs_stats as for dfs_batch"""
+        return self.dfs_batch([seed], max_depth, direction)[1:]
 
     def select_program(self, prog):
         """selector_eval (src/graph_selector_eval.c:511-543) for a resolved program, a list of (op, node, depth_up,
