@@ -23,8 +23,9 @@
 //   key[slot][node] is 32 bits: 0 visited, 0xFFFFFFFF untouched, anything else this level's claim.  It is filled once per
 //   allocation; after a chunk only the entries the chunk's output names are reset.  A stable sort of the pool by seed slot
 //   (level slices keep their order) gives the seed-major rows.
-#include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
+#include "mn_prim.hpp"
+#include "mn_traverse.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -41,34 +42,21 @@ typedef unsigned long long bfs_u64;
 #define BFS_BYTES_PER_NODE_SLOT ((size_t)64)     // scratch a seed slot may come to need, per node (include/muninn_hip.h)
 
 struct BfsWork {
-    unsigned *key = nullptr; // [key_slots][n]
-    size_t key_slots = 0;
-    bool key_clean = false;  // every entry is BFS_UNTOUCHED
-    int *p_node = nullptr, *p_parent = nullptr, *p_slot = nullptr, *p_depth = nullptr; // the pool, [pool_cap]
-    size_t pool_cap = 0;
-    bfs_u64 *iscan = nullptr; // [iscan_cap] inclusive degree sums of the frontier
-    size_t iscan_cap = 0;
-    bfs_u64 *seg_e = nullptr; // [slot_cap] first edge of a seed's part of the level's enumeration
-    int *d_seeds = nullptr;   // [slot_cap]
-    long long *d_rowoff = nullptr; // [slot_cap]
-    size_t slot_cap = 0;
-    unsigned *range_cnt = nullptr; // [BFS_MAX_RANGES]
-    bfs_u64 *tot = nullptr;        // [0] edges of the level, [1] wins of the level, [2] edges scanned so far
-    void *tmp = nullptr;           // rocPRIM's
-    size_t tmp_bytes = 0;
-    std::vector<int> r_node, r_depth, r_parent; // the rows of the last call
-    bool rows_valid = false;
+    DevBuf<unsigned> key;   // [slots][n], slots = key.cap / n
+    bool key_clean = false; // every entry is BFS_UNTOUCHED
+    DevBuf<int> p_node, p_parent, p_slot, p_depth; // the pool: four columns of pool_cap() entries
+    DevBuf<bfs_u64> iscan;       // inclusive degree sums of the frontier
+    DevBuf<bfs_u64> seg_e;       // [slots] first edge of a seed's part of the level's enumeration
+    DevBuf<int> d_seeds;         // [slots]
+    DevBuf<long long> d_rowoff;  // [slots]
+    DevBuf<unsigned> range_cnt;  // [BFS_MAX_RANGES]
+    DevBuf<bfs_u64> tot;         // [0] edges of the level, [1] wins of the level, [2] edges scanned so far
+    DevBuf<char> tmp;            // rocPRIM's
+    TravRows rows;               // of the last call
+    size_t pool_cap() const { return std::min(std::min(p_node.cap, p_parent.cap), std::min(p_slot.cap, p_depth.cap)); }
 };
 
-void bfs_work_free(BfsWork *w) {
-    if (!w)
-        return;
-    (void)hipFree(w->key);
-    (void)hipFree(w->p_node); (void)hipFree(w->p_parent); (void)hipFree(w->p_slot); (void)hipFree(w->p_depth);
-    (void)hipFree(w->iscan); (void)hipFree(w->seg_e); (void)hipFree(w->d_seeds); (void)hipFree(w->d_rowoff);
-    (void)hipFree(w->range_cnt); (void)hipFree(w->tot); (void)hipFree(w->tmp);
-    delete w;
-}
+void bfs_work_free(BfsWork *w) { delete w; }
 
 // ───────────────────────── kernels ─────────────────────────
 
@@ -276,48 +264,18 @@ __global__ void __launch_bounds__(BFS_BLOCK) k_bfs_gather(long long used, const 
 
 // ───────────────────────── host ─────────────────────────
 
-// a device array of the handle to at least `need` elements (half as much again when it grows), its first `keep` kept
-template <typename T> static int bfs_fit(T **p, size_t *cap, size_t need, size_t keep, hipStream_t st) {
-    if (need <= *cap)
-        return 0;
-    const size_t ncap = std::max(need, *cap + *cap / 2);
-    T *q = nullptr;
-    if (hipMalloc(&q, ncap * sizeof(T)) != hipSuccess) {
-        gset_err("mn_graph_bfs: out of device memory (%zu bytes)", ncap * sizeof(T));
-        return -1;
-    }
-    hipError_t e = keep ? hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, st) : hipSuccess;
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st); // (nothing in flight reads the old array once this returns)
-    if (e != hipSuccess) {
-        (void)hipFree(q);
-        gset_err("mn_graph_bfs: growing a device array failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    (void)hipFree(*p);
-    *p = q;
-    *cap = ncap;
-    return 0;
-}
+#define BFS_WHO "mn_graph_bfs"
 
-// the four pool arrays to `need` entries, the first `keep` kept
+// the pool's four columns to `need` entries (twice what it had, if that is more), the first `keep` kept.  A column that
+// fails leaves the others grown: pool_cap() is the smallest of the four, and the next call takes them on from where they are.
 static int bfs_pool_fit(BfsWork *w, size_t need, size_t keep, hipStream_t st) {
-    if (need <= w->pool_cap)
+    if (need <= w->pool_cap())
         return 0;
-    size_t c1 = w->pool_cap, c2 = w->pool_cap, c3 = w->pool_cap, c4 = w->pool_cap;
-    const size_t ncap = std::max(need, w->pool_cap * 2);
-    if (bfs_fit(&w->p_node, &c1, ncap, keep, st) || bfs_fit(&w->p_parent, &c2, ncap, keep, st) ||
-        bfs_fit(&w->p_slot, &c3, ncap, keep, st) || bfs_fit(&w->p_depth, &c4, ncap, keep, st)) {
-        w->pool_cap = std::min(std::min(c1, c2), std::min(c3, c4));
-        return -1;
-    }
-    w->pool_cap = ncap;
+    const size_t ncap = std::max(need, w->pool_cap() * 2);
+    for (DevBuf<int> *col : {&w->p_node, &w->p_parent, &w->p_slot, &w->p_depth})
+        if (col->grow(gset_err, BFS_WHO, ncap, keep, st))
+            return -1;
     return 0;
-}
-
-static unsigned bfs_grid(bfs_u64 items, unsigned per_block, unsigned max_blocks) {
-    const bfs_u64 b = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<bfs_u64>(1, std::min<bfs_u64>(b, max_blocks));
 }
 
 extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, const int *seeds, int max_depth, int64_t *row_off,
@@ -327,93 +285,47 @@ extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, con
     if (stats)
         memset(stats, 0, sizeof(*stats));
     if (g->bfs)
-        g->bfs->rows_valid = false;
-    if (direction < 0 || direction > 2) {
-        gset_err("mn_graph_bfs: direction must be 0 (both), 1 (forward) or 2 (reverse)");
+        g->bfs->rows.valid = false;
+    int use_out, use_in;
+    if (trav_check_args(BFS_WHO, g, direction, n_seeds, seeds, row_off, &use_out, &use_in))
         return -1;
-    }
-    if (n_seeds < 0 || (n_seeds > 0 && !seeds) || !row_off) {
-        gset_err("mn_graph_bfs: bad arguments (n_seeds = %lld)", (long long)n_seeds);
-        return -1;
-    }
-    if (N > (1 << 26)) {
-        gset_err("mn_graph_bfs: more than 2^26 nodes (N = %d)", N);
-        return -1;
-    }
     if ((bfs_u64)g->e_out + (bfs_u64)g->e_in > 0xFFFFFFFFull - 2) { // e_local + 1 must stay below the "untouched" word
         gset_err("mn_graph_bfs: more than 2^32 - 3 list entries");
         return -1;
     }
-    const int use_out = direction != 2, use_in = direction == 2 || direction == 0; // as mn_graph_betweenness
-    // a graph loaded for another direction (graph_data_load fills only the lists its direction traverses) has no answer here
-    if ((direction == 1 && g->e_out == 0 && g->e_in > 0) || (direction == 2 && g->e_in == 0 && g->e_out > 0) ||
-        (direction == 0 && g->e_out != g->e_in)) {
-        gset_err("mn_graph_bfs: the graph does not hold the %s this direction traverses (%lld out entries, %lld in entries)",
-                 direction == 1 ? "out-lists" : direction == 2 ? "in-lists" : "out- and in-lists", g->e_out, g->e_in);
+    if (trav_check_seeds(BFS_WHO, g, direction, n_seeds, seeds))
         return -1;
-    }
-    for (int64_t i = 0; i < n_seeds; i++)
-        if (seeds[i] < 0 || seeds[i] >= N) {
-            gset_err("mn_graph_bfs: seed %lld is node %d, outside 0 .. %d", (long long)i, seeds[i], N - 1);
-            return -1;
-        }
     if (!g->bfs)
         g->bfs = new BfsWork();
     BfsWork *w = g->bfs;
-    w->r_node.clear();
-    w->r_depth.clear();
-    w->r_parent.clear();
+    w->rows.clear();
     g->last_ms = 0;
-    if (n_seeds == 0) {
-        row_off[0] = 0;
-        w->rows_valid = true;
-        return 0;
-    }
-    if (max_depth <= 0) { // the start rows and nothing else (:282)
-        w->r_node.assign(seeds, seeds + n_seeds);
-        w->r_depth.assign((size_t)n_seeds, 0);
-        w->r_parent.assign((size_t)n_seeds, -1);
-        for (int64_t i = 0; i <= n_seeds; i++)
-            row_off[i] = i;
+    if (n_seeds == 0 || max_depth <= 0) { // no launch: the start rows and nothing else (:282)
+        w->rows.seeds_only(n_seeds, seeds, row_off);
         if (stats)
             stats->rows = n_seeds;
-        w->rows_valid = true;
         return n_seeds;
     }
     hipStream_t st = g->stream;
     const size_t per_slot = BFS_BYTES_PER_NODE_SLOT * (size_t)N;
-    const size_t S = std::max<size_t>(1, std::min<size_t>({(size_t)n_seeds, scratch_budget("MN_BFS_SCRATCH_MB", 0) / per_slot, (size_t)0x7fffffff / (size_t)N}));
-    if (w->key_slots < S) {
-        (void)hipFree(w->key);
-        w->key = nullptr;
-        w->key_slots = 0;
-        if (hipMalloc(&w->key, S * (size_t)N * sizeof(unsigned)) != hipSuccess) {
+    const size_t S = scratch_chunk((size_t)n_seeds, scratch_budget("MN_BFS_SCRATCH_MB", 0), per_slot, (size_t)0x7fffffff / (size_t)N);
+    if (w->key.cap < S * (size_t)N) {
+        w->key_clean = false;
+        if (w->key.fit(gset_err, BFS_WHO, S * (size_t)N)) {
             gset_err("mn_graph_bfs: out of device memory (N = %d, %zu seeds at once)", N, S);
             return -1;
         }
-        w->key_slots = S;
-        w->key_clean = false;
     }
-    if (w->slot_cap < S) {
-        size_t c1 = w->slot_cap, c2 = w->slot_cap, c3 = w->slot_cap;
-        if (bfs_fit(&w->seg_e, &c1, S, 0, st) || bfs_fit(&w->d_seeds, &c2, S, 0, st) || bfs_fit(&w->d_rowoff, &c3, S, 0, st)) {
-            w->slot_cap = 0; // (the three may differ now: all of them are fitted again next time)
-            return -1;
-        }
-        w->slot_cap = std::min(c1, std::min(c2, c3));
-    }
-    if (!w->range_cnt && hipMalloc(&w->range_cnt, BFS_MAX_RANGES * sizeof(unsigned)) != hipSuccess) {
-        gset_err("mn_graph_bfs: out of device memory");
+    if (w->seg_e.fit(gset_err, BFS_WHO, S) || w->d_seeds.fit(gset_err, BFS_WHO, S) || w->d_rowoff.fit(gset_err, BFS_WHO, S))
         return -1;
-    }
-    if (!w->tot && hipMalloc(&w->tot, 4 * sizeof(bfs_u64)) != hipSuccess) {
+    if (w->range_cnt.fit(gset_err, BFS_WHO, BFS_MAX_RANGES) || w->tot.fit(gset_err, BFS_WHO, 4)) {
         gset_err("mn_graph_bfs: out of device memory");
         return -1;
     }
     if (bfs_pool_fit(w, std::min<size_t>(S * (size_t)N, std::max<size_t>(S * 64, (size_t)1 << 20)), 0, st))
         return -1;
     if (!w->key_clean) {
-        GCHK(hipMemsetAsync(w->key, 0xFF, w->key_slots * (size_t)N * sizeof(unsigned), st));
+        GCHK(hipMemsetAsync(w->key, 0xFF, w->key.cap * sizeof(unsigned), st));
         w->key_clean = true;
     }
     const int max_deg = use_in ? g->max_deg_both : g->max_deg_out; // (out + in bounds the in-lists alone too)
@@ -441,7 +353,7 @@ extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, con
         long long f0 = 0, F = Sc; // the frontier: pool[f0 .. f0 + F)
         bfs_u64 h_tot[3] = {0, 0, 0};
         for (int depth = 1; depth <= max_depth && F > 0; depth++) {
-            if (bfs_fit(&w->iscan, &w->iscan_cap, (size_t)F, 0, st))
+            if ((size_t)F > w->iscan.cap && w->iscan.fit(gset_err, BFS_WHO, std::max((size_t)F, w->iscan.cap + w->iscan.cap / 2)))
                 return -1;
             a.p_node = w->p_node;
             a.p_parent = w->p_parent;
@@ -451,39 +363,21 @@ extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, con
             a.F = F;
             a.iscan = w->iscan;
             a.depth = depth;
-            auto degs = rocprim::make_transform_iterator(w->p_node + f0, deg_of);
-            size_t need = 0;
-            if (rocprim::inclusive_scan(nullptr, need, degs, w->iscan, (size_t)F, rocprim::plus<bfs_u64>(), st) != hipSuccess) {
-                gset_err("rocprim::inclusive_scan (size query) failed");
+            auto degs = rocprim::make_transform_iterator(w->p_node.p + f0, deg_of);
+            if (prim_run(BFS_WHO, "rocprim::inclusive_scan", w->tmp, st, [&](void *tmp, size_t &bytes) {
+                    return rocprim::inclusive_scan(tmp, bytes, degs, w->iscan.p, (size_t)F, rocprim::plus<bfs_u64>(), st);
+                }))
                 return -1;
-            }
-            if (need > w->tmp_bytes) {
-                GCHK(hipStreamSynchronize(st));
-                (void)hipFree(w->tmp);
-                w->tmp = nullptr;
-                w->tmp_bytes = 0;
-                if (hipMalloc(&w->tmp, need) != hipSuccess) {
-                    gset_err("mn_graph_bfs: out of device memory (%zu bytes)", need);
-                    return -1;
-                }
-                w->tmp_bytes = need;
-            }
-            if (rocprim::inclusive_scan(w->tmp, need, degs, w->iscan, (size_t)F, rocprim::plus<bfs_u64>(), st) != hipSuccess) {
-                gset_err("rocprim::inclusive_scan failed");
-                return -1;
-            }
-            hipLaunchKernelGGL(k_bfs_segments, dim3(bfs_grid((bfs_u64)F, BFS_BLOCK, 0x7fffffffu)), dim3(BFS_BLOCK), 0, st, a, w->seg_e);
+            hipLaunchKernelGGL(k_bfs_segments, dim3(launch_blocks((bfs_u64)F, BFS_BLOCK, 0x7fffffffu)), dim3(BFS_BLOCK), 0, st, a, w->seg_e);
             const bfs_u64 e_bound = (bfs_u64)F * (bfs_u64)std::max(1, max_deg);
-            hipLaunchKernelGGL(k_bfs_claim, dim3(bfs_grid(e_bound, BFS_BLOCK, 8192)), dim3(BFS_BLOCK), 0, st, a);
-            const unsigned ranges = bfs_grid(e_bound, BFS_BLOCK * 8, BFS_MAX_RANGES);
+            hipLaunchKernelGGL(k_bfs_claim, dim3(launch_blocks(e_bound, BFS_BLOCK, 8192)), dim3(BFS_BLOCK), 0, st, a);
+            const unsigned ranges = launch_blocks(e_bound, BFS_BLOCK * 8, BFS_MAX_RANGES);
             hipLaunchKernelGGL(k_bfs_count, dim3(ranges), dim3(BFS_BLOCK), 0, st, a);
-            GCHK(hipEventRecord(g->ev1, st));
-            GCHK(hipGetLastError());
+            if (graph_mark(g))
+                return -1;
             GCHK(hipMemcpyAsync(h_tot, w->tot, sizeof(h_tot), hipMemcpyDeviceToHost, st)); // the level's one round trip
-            GCHK(hipStreamSynchronize(st));
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-                device_ms += ms;
+            if (graph_wait(g, &device_ms))
+                return -1;
             levels++;
             const long long W = (long long)h_tot[1];
             if (bfs_pool_fit(w, (size_t)(f0 + F + W), (size_t)(f0 + F), st))
@@ -508,40 +402,26 @@ extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, con
         int bits = 1;
         while (bits < 31 && ((long long)1 << bits) < Sc)
             bits++;
-        size_t sort_bytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, sort_bytes, w->p_slot, slot_sorted, idx, order, (size_t)used, 0, bits, st) != hipSuccess) {
-            gset_err("rocprim::radix_sort_pairs (size query) failed");
-            return -1;
-        }
-        void *sort_tmp = scr.alloc<char>(sort_bytes);
-        if (!slot_sorted || !idx || !order || !o_node || !o_depth || !o_parent || !sort_tmp) {
+        if (!slot_sorted || !idx || !order || !o_node || !o_depth || !o_parent) {
             gset_err("mn_graph_bfs: out of device memory (%lld rows in one chunk)", used);
             return -1;
         }
-        const dim3 grid_u(bfs_grid((bfs_u64)used, BFS_BLOCK, 0x7fffffffu));
+        const dim3 grid_u(launch_blocks((bfs_u64)used, BFS_BLOCK, 0x7fffffffu));
         hipLaunchKernelGGL(k_bfs_iota, grid_u, dim3(BFS_BLOCK), 0, st, used, idx);
-        if (rocprim::radix_sort_pairs(sort_tmp, sort_bytes, w->p_slot, slot_sorted, idx, order, (size_t)used, 0, bits, st) != hipSuccess) {
-            gset_err("rocprim::radix_sort_pairs failed");
+        if (prim_run(BFS_WHO, "rocprim::radix_sort_pairs", w->tmp, st, [&](void *tmp, size_t &bytes) {
+                return rocprim::radix_sort_pairs(tmp, bytes, w->p_slot.p, slot_sorted, idx, order, (size_t)used, 0, bits, st);
+            }))
             return -1;
-        }
         hipLaunchKernelGGL(k_bfs_gather, grid_u, dim3(BFS_BLOCK), 0, st, used, order, slot_sorted, w->p_node, w->p_depth, w->p_parent,
                            o_node, o_depth, o_parent, w->d_rowoff);
         hipLaunchKernelGGL(k_bfs_reset, grid_u, dim3(BFS_BLOCK), 0, st, used, N, w->p_node, w->p_slot, w->key);
-        GCHK(hipEventRecord(g->ev1, st));
-        GCHK(hipGetLastError());
-        w->r_node.resize((size_t)(rows + used));
-        w->r_depth.resize((size_t)(rows + used));
-        w->r_parent.resize((size_t)(rows + used));
+        if (graph_mark(g) || w->rows.append(st, (size_t)used, o_node, o_depth, o_parent))
+            return -1;
         h_rowoff.resize((size_t)Sc);
-        GCHK(hipMemcpyAsync(w->r_node.data() + rows, o_node, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(w->r_depth.data() + rows, o_depth, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(w->r_parent.data() + rows, o_parent, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
         GCHK(hipMemcpyAsync(h_rowoff.data(), w->d_rowoff, (size_t)Sc * sizeof(long long), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
+        if (graph_wait(g, &device_ms))
+            return -1;
         w->key_clean = true;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-            device_ms += ms;
         for (int s = 0; s < Sc; s++)
             row_off[s0 + s] = rows + h_rowoff[(size_t)s];
         rows += used;
@@ -555,24 +435,10 @@ extern "C" int64_t mn_graph_bfs(mn_graph *g, int direction, int64_t n_seeds, con
         stats->edges_scanned = edges;
         stats->device_ms = device_ms;
     }
-    w->rows_valid = true;
+    w->rows.valid = true;
     return rows;
 } MN_GUARD_END(gset_err, MN_NOTHING, -1)
 
 extern "C" int mn_graph_bfs_rows(mn_graph *g, int *node, int *depth, int *parent) try {
-    const BfsWork *w = g->bfs;
-    if (!w || !w->rows_valid) {
-        gset_err("mn_graph_bfs_rows: no rows (the last mn_graph_bfs on this graph failed, or there was none)");
-        return -1;
-    }
-    const size_t bytes = w->r_node.size() * sizeof(int);
-    if (bytes) {
-        if (node)
-            memcpy(node, w->r_node.data(), bytes);
-        if (depth)
-            memcpy(depth, w->r_depth.data(), bytes);
-        if (parent)
-            memcpy(parent, w->r_parent.data(), bytes);
-    }
-    return 0;
+    return trav_rows_out(g->bfs ? &g->bfs->rows : nullptr, BFS_WHO, node, depth, parent);
 } MN_GUARD_END(gset_err, MN_NOTHING, -1)

@@ -257,11 +257,9 @@ extern "C" int mn_graph_betweenness(mn_graph *g, int direction, int auto_approx,
     const int N = g->n;
     if (N == 0)
         return 0;
-    if (direction < 0 || direction > 2) {
-        gset_err("mn_graph_betweenness: direction must be 0 (both), 1 (forward) or 2 (reverse)");
+    int use_out, use_in; // :281-282
+    if (graph_direction("mn_graph_betweenness", direction, &use_out, &use_in))
         return -1;
-    }
-    const int use_out = direction != 2, use_in = direction == 2 || direction == 0; // :281-282
     hipStream_t st = g->stream;
     // source set (:417-433)
     std::vector<int> sources;
@@ -356,8 +354,8 @@ extern "C" int mn_graph_betweenness(mn_graph *g, int direction, int auto_approx,
     if (d_eb)
         hipLaunchKernelGGL(k_scale_d, dim3((unsigned)(((long long)N * N + 255) / 256)), dim3(256), 0, st, d_eb, (long long)N * N, scale,
                            half, norm);
-    GCHK(hipEventRecord(g->ev1, st));
-    GCHK(hipGetLastError());
+    if (graph_mark(g))
+        return -1;
     int ovf = 0;
     GCHK(hipMemcpyAsync(&ovf, a.overflow, sizeof(int), hipMemcpyDeviceToHost, st));
     GCHK(hipMemcpyAsync(cb_out, d_cb, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -569,15 +567,13 @@ extern "C" int mn_graph_closeness(mn_graph *g, int direction, int normalized, do
     const int N = g->n;
     if (N == 0)
         return 0;
-    if (direction < 0 || direction > 2) {
-        gset_err("mn_graph_closeness: direction must be 0 (both), 1 (forward) or 2 (reverse)");
+    int use_out, use_in; // :278-279
+    if (graph_direction("mn_graph_closeness", direction, &use_out, &use_in))
         return -1;
-    }
     if (N > (1 << 26)) { // (N - 1)^2 bounds sum_dist: past this it leaves the range in which every integer is a double
         gset_err("mn_graph_closeness: more than 2^26 nodes (N = %d)", N);
         return -1;
     }
-    const int use_out = direction != 2, use_in = direction == 2 || direction == 0; // :278-279
     hipStream_t st = g->stream;
     DevArena scr;
     const DevGraph dg = dev_graph_of(g);
@@ -589,7 +585,7 @@ extern "C" int mn_graph_closeness(mn_graph *g, int direction, int normalized, do
         const long long nb_total = ((long long)N + 63) / 64;
         const size_t per_batch = (size_t)N * 3 * sizeof(clo_word);
         // (at most 2^30 words per array: every launch below then stays inside the 2^32 threads a grid may have)
-        const int B = (int)std::max<size_t>(1, std::min<size_t>({(size_t)nb_total, budget / per_batch, ((size_t)1 << 30) / (size_t)N}));
+        const int B = (int)scratch_chunk((size_t)nb_total, budget, per_batch, ((size_t)1 << 30) / (size_t)N);
         clo_word *seen = scr.alloc<clo_word>((size_t)N * B);
         clo_word *frontier = scr.alloc<clo_word>((size_t)N * B);
         clo_word *next = scr.alloc<clo_word>((size_t)N * B);
@@ -649,8 +645,8 @@ extern "C" int mn_graph_closeness(mn_graph *g, int direction, int normalized, do
         }
         GCHK(hipMemcpyAsync(&ovf, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
     }
-    GCHK(hipEventRecord(g->ev1, st));
-    GCHK(hipGetLastError());
+    if (graph_mark(g))
+        return -1;
     GCHK(hipMemcpyAsync(out, d_cc, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
     GCHK(hipStreamSynchronize(st));
     if (ovf) {

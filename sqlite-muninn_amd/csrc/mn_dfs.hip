@@ -27,8 +27,9 @@
 //
 // Every slot counts its steps against (list entries followed) + 2 n + 2; a slot that overruns stops and sets its status word,
 // and the host reports an internal error.  No loop spins without that bound.
-#include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
+#include "mn_prim.hpp"
+#include "mn_traverse.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -44,27 +45,17 @@ typedef unsigned long long dfs_u64;
 #define DFS_INFO 4
 
 struct DfsWork {
-    int *rows = nullptr;        // [slots][3][n]: a slot's node, depth and parent columns
-    unsigned *vis = nullptr;    // [slots][words]: the visited bitmaps
-    int2 *frames = nullptr;     // [slots][frames_per]: (u, cursor) of the frames below the top one
-    size_t rows_cap = 0, vis_cap = 0, frames_cap = 0; // elements
-    int *d_seeds = nullptr, *cnt = nullptr; // [slot_cap], [slot_cap + 1]
-    long long *rowoff = nullptr;            // [slot_cap + 1]
-    dfs_u64 *info = nullptr;                // [slot_cap][DFS_INFO]
-    size_t slot_cap = 0;
-    void *tmp = nullptr; // rocPRIM's
-    size_t tmp_bytes = 0;
-    std::vector<int> r_node, r_depth, r_parent; // the rows of the last call
-    bool rows_valid = false;
+    DevBuf<int> slot_rows;      // [slots][3][n]: a slot's node, depth and parent columns
+    DevBuf<unsigned> vis;       // [slots][words]: the visited bitmaps
+    DevBuf<int2> frames;        // [slots][frames_per]: (u, cursor) of the frames below the top one
+    DevBuf<int> d_seeds, cnt;   // [slots], [slots + 1]
+    DevBuf<long long> rowoff;   // [slots + 1]
+    DevBuf<dfs_u64> info;       // [slots][DFS_INFO]
+    DevBuf<char> tmp;           // rocPRIM's
+    TravRows rows;              // of the last call
 };
 
-void dfs_work_free(DfsWork *w) {
-    if (!w)
-        return;
-    (void)hipFree(w->rows); (void)hipFree(w->vis); (void)hipFree(w->frames);
-    (void)hipFree(w->d_seeds); (void)hipFree(w->cnt); (void)hipFree(w->rowoff); (void)hipFree(w->info); (void)hipFree(w->tmp);
-    delete w;
-}
+void dfs_work_free(DfsWork *w) { delete w; }
 
 // ───────────────────────── kernels ─────────────────────────
 
@@ -241,21 +232,7 @@ __global__ void __launch_bounds__(DFS_BLOCK) k_dfs_rows(int S, int n, long long 
 
 // ───────────────────────── host ─────────────────────────
 
-// a device array of the handle to at least `need` elements; what it held is not kept
-template <typename T> static int dfs_fit(T **p, size_t *cap, size_t need) {
-    if (need <= *cap)
-        return 0;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        gset_err("mn_graph_dfs: out of device memory (%zu bytes)", need * sizeof(T));
-        return -1;
-    }
-    *cap = need;
-    return 0;
-}
+#define DFS_WHO "mn_graph_dfs"
 
 extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, const int *seeds, int max_depth, int64_t *row_off,
                                 mn_dfs_stats *stats) try {
@@ -264,79 +241,36 @@ extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, con
     if (stats)
         memset(stats, 0, sizeof(*stats));
     if (g->dfs)
-        g->dfs->rows_valid = false;
-    if (direction < 0 || direction > 2) {
-        gset_err("mn_graph_dfs: direction must be 0 (both), 1 (forward) or 2 (reverse)");
+        g->dfs->rows.valid = false;
+    int use_out, use_in;
+    if (trav_check_args(DFS_WHO, g, direction, n_seeds, seeds, row_off, &use_out, &use_in))
         return -1;
-    }
-    if (n_seeds < 0 || (n_seeds > 0 && !seeds) || !row_off) {
-        gset_err("mn_graph_dfs: bad arguments (n_seeds = %lld)", (long long)n_seeds);
-        return -1;
-    }
-    if (N > (1 << 26)) {
-        gset_err("mn_graph_dfs: more than 2^26 nodes (N = %d)", N);
-        return -1;
-    }
-    const int use_out = direction != 2, use_in = direction == 2 || direction == 0; // as mn_graph_bfs
     const dfs_u64 followed = (use_out ? (dfs_u64)g->e_out : 0) + (use_in ? (dfs_u64)g->e_in : 0);
     if (followed >= ((dfs_u64)1 << 31)) { // a cursor is a 32-bit count of a node's entries
         gset_err("mn_graph_dfs: 2^31 or more list entries in the lists this direction follows");
         return -1;
     }
-    if ((direction == 1 && g->e_out == 0 && g->e_in > 0) || (direction == 2 && g->e_in == 0 && g->e_out > 0) ||
-        (direction == 0 && g->e_out != g->e_in)) {
-        gset_err("mn_graph_dfs: the graph does not hold the %s this direction traverses (%lld out entries, %lld in entries)",
-                 direction == 1 ? "out-lists" : direction == 2 ? "in-lists" : "out- and in-lists", g->e_out, g->e_in);
+    if (trav_check_seeds(DFS_WHO, g, direction, n_seeds, seeds))
         return -1;
-    }
-    for (int64_t i = 0; i < n_seeds; i++)
-        if (seeds[i] < 0 || seeds[i] >= N) {
-            gset_err("mn_graph_dfs: seed %lld is node %d, outside 0 .. %d", (long long)i, seeds[i], N - 1);
-            return -1;
-        }
     if (!g->dfs)
         g->dfs = new DfsWork();
     DfsWork *w = g->dfs;
-    w->r_node.clear();
-    w->r_depth.clear();
-    w->r_parent.clear();
+    w->rows.clear();
     g->last_ms = 0;
-    if (n_seeds == 0) {
-        row_off[0] = 0;
-        w->rows_valid = true;
-        return 0;
-    }
-    if (max_depth <= 0) { // the start rows and nothing else (:383)
-        w->r_node.assign(seeds, seeds + n_seeds);
-        w->r_depth.assign((size_t)n_seeds, 0);
-        w->r_parent.assign((size_t)n_seeds, -1);
-        for (int64_t i = 0; i <= n_seeds; i++)
-            row_off[i] = i;
+    if (n_seeds == 0 || max_depth <= 0) { // no launch: the start rows and nothing else (:383)
+        w->rows.seeds_only(n_seeds, seeds, row_off);
         if (stats)
             stats->rows = n_seeds;
-        w->rows_valid = true;
         return n_seeds;
     }
     hipStream_t st = g->stream;
     const size_t words = ((size_t)N + 31) / 32, frames_per = (size_t)std::min(N, max_depth);
     const size_t per_slot = 12 * (size_t)N + words * 4 + 8 * frames_per;
-    const size_t S = std::max<size_t>(1, std::min<size_t>({(size_t)n_seeds, scratch_budget("MN_DFS_SCRATCH_MB", 0) / per_slot, (size_t)0x7fffffff}));
-    if (dfs_fit(&w->rows, &w->rows_cap, S * 3 * (size_t)N) || dfs_fit(&w->vis, &w->vis_cap, S * words) ||
-        dfs_fit(&w->frames, &w->frames_cap, S * frames_per))
+    const size_t S = scratch_chunk((size_t)n_seeds, scratch_budget("MN_DFS_SCRATCH_MB", 0), per_slot, (size_t)0x7fffffff);
+    if (w->slot_rows.fit(gset_err, DFS_WHO, S * 3 * (size_t)N) || w->vis.fit(gset_err, DFS_WHO, S * words) ||
+        w->frames.fit(gset_err, DFS_WHO, S * frames_per) || w->d_seeds.fit(gset_err, DFS_WHO, S) ||
+        w->cnt.fit(gset_err, DFS_WHO, S + 1) || w->rowoff.fit(gset_err, DFS_WHO, S + 1) || w->info.fit(gset_err, DFS_WHO, S * DFS_INFO))
         return -1;
-    if (w->slot_cap < S) {
-        size_t c1 = w->slot_cap, c2 = w->slot_cap ? w->slot_cap + 1 : 0, c3 = c2, c4 = w->slot_cap * DFS_INFO;
-        const int bad = dfs_fit(&w->d_seeds, &c1, S) || dfs_fit(&w->cnt, &c2, S + 1) || dfs_fit(&w->rowoff, &c3, S + 1) ||
-                        dfs_fit(&w->info, &c4, S * DFS_INFO);
-        w->slot_cap = bad ? 0 : S; // (after a failure the four may differ: all of them are fitted again next time)
-        if (bad) {
-            (void)hipFree(w->d_seeds); (void)hipFree(w->cnt); (void)hipFree(w->rowoff); (void)hipFree(w->info);
-            w->d_seeds = w->cnt = nullptr;
-            w->rowoff = nullptr;
-            w->info = nullptr;
-            return -1;
-        }
-    }
     int64_t rows = 0, chunks = 0, entries = 0, max_frames = 0;
     double device_ms = 0;
     std::vector<long long> h_rowoff;
@@ -355,7 +289,7 @@ extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, con
         a.frames_per = frames_per;
         a.step_bound = followed + 2 * (dfs_u64)N + 2;
         a.seeds = w->d_seeds;
-        a.rows = w->rows;
+        a.rows = w->slot_rows;
         a.vis = w->vis;
         a.frames = w->frames;
         a.cnt = w->cnt;
@@ -365,39 +299,17 @@ extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, con
         GCHK(hipMemsetAsync(w->vis, 0, (size_t)Sc * words * sizeof(unsigned), st));
         GCHK(hipMemsetAsync(w->cnt, 0, ((size_t)Sc + 1) * sizeof(int), st));
         hipLaunchKernelGGL(k_dfs, dim3((unsigned)Sc), dim3(DFS_WAVE), 0, st, a);
-        size_t need = 0;
-        if (rocprim::exclusive_scan(nullptr, need, w->cnt, w->rowoff, (long long)0, (size_t)Sc + 1, rocprim::plus<long long>(), st) !=
-            hipSuccess) {
-            gset_err("rocprim::exclusive_scan (size query) failed");
+        if (prim_run(DFS_WHO, "rocprim::exclusive_scan", w->tmp, st, [&](void *tmp, size_t &bytes) {
+                return rocprim::exclusive_scan(tmp, bytes, w->cnt.p, w->rowoff.p, (long long)0, (size_t)Sc + 1, rocprim::plus<long long>(), st);
+            }) ||
+            graph_mark(g))
             return -1;
-        }
-        if (need > w->tmp_bytes) {
-            GCHK(hipStreamSynchronize(st));
-            (void)hipFree(w->tmp);
-            w->tmp = nullptr;
-            w->tmp_bytes = 0;
-            if (hipMalloc(&w->tmp, need) != hipSuccess) {
-                w->tmp = nullptr;
-                gset_err("mn_graph_dfs: out of device memory (%zu bytes)", need);
-                return -1;
-            }
-            w->tmp_bytes = need;
-        }
-        if (rocprim::exclusive_scan(w->tmp, need, w->cnt, w->rowoff, (long long)0, (size_t)Sc + 1, rocprim::plus<long long>(), st) !=
-            hipSuccess) {
-            gset_err("rocprim::exclusive_scan failed");
-            return -1;
-        }
-        GCHK(hipEventRecord(g->ev1, st));
-        GCHK(hipGetLastError());
         h_rowoff.resize((size_t)Sc + 1);
         h_info.resize((size_t)Sc * DFS_INFO);
         GCHK(hipMemcpyAsync(h_rowoff.data(), w->rowoff, ((size_t)Sc + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
         GCHK(hipMemcpyAsync(h_info.data(), w->info, (size_t)Sc * DFS_INFO * sizeof(dfs_u64), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-            device_ms += ms;
+        if (graph_wait(g, &device_ms))
+            return -1;
         for (int s = 0; s < Sc; s++) {
             const dfs_u64 *f = &h_info[(size_t)s * DFS_INFO];
             if (f[2] != 0) {
@@ -415,20 +327,11 @@ extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, con
             gset_err("mn_graph_dfs: out of device memory (%lld rows in one chunk)", used);
             return -1;
         }
-        w->r_node.resize((size_t)(rows + used));
-        w->r_depth.resize((size_t)(rows + used));
-        w->r_parent.resize((size_t)(rows + used));
         GCHK(hipEventRecord(g->ev0, st));
         hipLaunchKernelGGL(k_dfs_rows, dim3((unsigned)((used + DFS_BLOCK - 1) / DFS_BLOCK)), dim3(DFS_BLOCK), 0, st, Sc, N, used, w->rowoff,
-                           w->rows, o_node, o_depth, o_parent);
-        GCHK(hipEventRecord(g->ev1, st));
-        GCHK(hipGetLastError());
-        GCHK(hipMemcpyAsync(w->r_node.data() + rows, o_node, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(w->r_depth.data() + rows, o_depth, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipMemcpyAsync(w->r_parent.data() + rows, o_parent, (size_t)used * sizeof(int), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-            device_ms += ms;
+                           w->slot_rows, o_node, o_depth, o_parent);
+        if (graph_mark(g) || w->rows.append(st, (size_t)used, o_node, o_depth, o_parent) || graph_wait(g, &device_ms))
+            return -1;
         for (int s = 0; s < Sc; s++)
             row_off[s0 + s] = rows + h_rowoff[(size_t)s];
         rows += used;
@@ -442,24 +345,10 @@ extern "C" int64_t mn_graph_dfs(mn_graph *g, int direction, int64_t n_seeds, con
         stats->max_frames = max_frames;
         stats->device_ms = device_ms;
     }
-    w->rows_valid = true;
+    w->rows.valid = true;
     return rows;
 } MN_GUARD_END(gset_err, MN_NOTHING, -1)
 
 extern "C" int mn_graph_dfs_rows(mn_graph *g, int *node, int *depth, int *parent) try {
-    const DfsWork *w = g->dfs;
-    if (!w || !w->rows_valid) {
-        gset_err("mn_graph_dfs_rows: no rows (the last mn_graph_dfs on this graph failed, or there was none)");
-        return -1;
-    }
-    const size_t bytes = w->r_node.size() * sizeof(int);
-    if (bytes) {
-        if (node)
-            memcpy(node, w->r_node.data(), bytes);
-        if (depth)
-            memcpy(depth, w->r_depth.data(), bytes);
-        if (parent)
-            memcpy(parent, w->r_parent.data(), bytes);
-    }
-    return 0;
+    return trav_rows_out(g->dfs ? &g->dfs->rows : nullptr, DFS_WHO, node, depth, parent);
 } MN_GUARD_END(gset_err, MN_NOTHING, -1)

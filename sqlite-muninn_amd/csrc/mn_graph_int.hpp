@@ -1,8 +1,14 @@
-// mn_graph_int.hpp — what the translation units behind the mn_graph handle share: mn_graph.hip (handle, CSR upload),
-// mn_csr_build.hip (the handle built on the device from an edge list),
-// mn_leiden.hip (with mn_leiden_eval.hpp, the device code of its evaluation, included by it alone), mn_centrality.hip and
-// mn_bfs.hip, mn_dfs.hip, mn_select.hip and mn_sssp.hip.  Host declarations and the kernels' view of the CSR only: device code does not cross a translation unit, every
-// kernel lives in the file that launches it.
+// mn_graph_int.hpp — what the translation units behind the mn_graph handle share:
+//   mn_graph.hip        the handle and the CSR upload
+//   mn_csr_build.hip    the handle built on the device from an edge list
+//   mn_leiden.hip       with mn_leiden_eval.hpp, the device code of its evaluation, which it alone includes
+//   mn_centrality.hip   betweenness, closeness, degree
+//   mn_bfs.hip, mn_dfs.hip (with mn_traverse.hpp: a seed traversal's argument checks and row store), mn_select.hip,
+//   mn_sssp.hip         the entry points that keep scratch and the rows of their last call with the handle
+// Here: the handle, the kernels' view of the CSR, the error string, and the host idioms every such entry point repeats —
+// the direction argument, device time between the handle's two events, the scratch budget and the chunk it admits, the
+// clamped grid size.  mn_host.hpp has the owned device array (DevBuf), mn_prim.hpp rocPRIM's two-phase call.  Host
+// declarations only: device code does not cross a translation unit, every kernel lives in the file that launches it.
 #pragma once
 #include "../../include/muninn_hip.h"
 #include "mn_host.hpp"
@@ -54,7 +60,35 @@ inline DevGraph dev_graph_of(const mn_graph *g) { return {g->n, g->off_out, g->t
 void gset_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 #define GCHK(expr) MN_HIPCHK(gset_err, expr)
 
-// device time between the handle's two events → mn_graph_last_ms
+// direction 0 (both), 1 (forward) or 2 (reverse) → the lists a traversal follows; anything else is `who`'s error
+inline int graph_direction(const char *who, int direction, int *use_out, int *use_in) {
+    if (direction < 0 || direction > 2) {
+        gset_err("%s: direction must be 0 (both), 1 (forward) or 2 (reverse)", who);
+        return -1;
+    }
+    *use_out = direction != 2;
+    *use_in = direction != 1;
+    return 0;
+}
+
+// Device time is what lies between the handle's two events.  The caller records ev0 where its launches begin;
+// graph_mark records ev1 behind them and picks up a launch error; graph_wait waits for the stream and adds ev0 .. ev1 to
+// *ms.  A read-back queued between the two rides on the same wait.
+inline int graph_mark(mn_graph *g) {
+    GCHK(hipEventRecord(g->ev1, g->stream));
+    GCHK(hipGetLastError());
+    return 0;
+}
+inline int graph_wait(mn_graph *g, double *ms) {
+    GCHK(hipStreamSynchronize(g->stream));
+    float t = 0;
+    if (hipEventElapsedTime(&t, g->ev0, g->ev1) == hipSuccess)
+        *ms += t;
+    return 0;
+}
+inline int graph_mark_wait(mn_graph *g, double *ms) { return graph_mark(g) || graph_wait(g, ms) ? -1 : 0; }
+
+// the same interval → mn_graph_last_ms, for a call that has waited already
 inline void graph_note_ms(mn_graph *g) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
@@ -72,6 +106,15 @@ inline size_t scratch_budget(const char *env, size_t reserve) {
         budget = mb > 0 ? (size_t)(mb * 1048576.0) : 0;
     }
     return budget;
+}
+// how many of `n` items go through at once at `per_item` bytes of scratch each: at least one, at most `cap`
+inline size_t scratch_chunk(size_t n, size_t budget, size_t per_item, size_t cap) {
+    return std::max<size_t>(1, std::min({n, budget / per_item, cap}));
+}
+
+// workgroups for `items` at `per_block` each: at least one, at most `max_blocks`
+inline unsigned launch_blocks(unsigned long long items, unsigned per_block, unsigned max_blocks) {
+    return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((items + per_block - 1) / per_block, max_blocks));
 }
 
 void lei_work_free(LeiWork *w); // mn_leiden.hip: releases and deletes a graph's Leiden workspace (mn_graph_destroy)

@@ -471,7 +471,7 @@ extern "C" int mn_vec_dist_batch(int metric, int order, const float *query, cons
     if (n <= 0)
         return 0;
     int ld = (dim + 3) & ~3;
-    DevBuf<float> dq, dr, dout; // released on every path
+    IndexBuf<float> dq, dr, dout; // released on every path
     if (dq.reserve((size_t)dim, false, nullptr) || dr.reserve((size_t)n * ld, false, nullptr) || dout.reserve((size_t)n, false, nullptr))
         return -1;
     HIPCHK(hipMemcpy(dq.p, query, (size_t)dim * sizeof(float), hipMemcpyHostToDevice));

@@ -18,14 +18,10 @@
 void set_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 #define HIPCHK(expr) MN_HIPCHK(set_err, expr)
 
-// one growable device allocation, freed with its owner
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0; // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
+// mn_host.hpp's owned device array with the index's way to a size: geometric steps, an optional fill, mn_last_error
+template <typename T> struct IndexBuf : DevBuf<T> {
+    using DevBuf<T>::p;
+    using DevBuf<T>::cap;
     // `want` (> n, optional): a size the caller knows the buffer will reach (a bulk build) — taken exactly, in ONE allocation,
     // instead of the geometric steps and their 1.5x slack
     int reserve(size_t n, bool keep, hipStream_t st, int fill_byte = -1, size_t want = 0) {
@@ -49,12 +45,6 @@ template <typename T> struct DevBuf {
         p = np;
         cap = nc;
         return 0;
-    }
-    void release() {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 
@@ -95,13 +85,13 @@ struct mn_index : MnStreamEvents {
     std::vector<int> ht;
     int ht_cap = 256;
     // device state
-    DevBuf<float> d_vectors, d_norms;
-    DevBuf<mn_lo_t> d_vec_lo;    // coded shadow of d_vectors (mn_lo_row_words(ld) dwords per row), grown with it (mn_lo_enabled(ld) only; mn_device.hpp MnLoMeta)
-    DevBuf<MnLoMeta> d_lo_meta;
-    DevBuf<int> d_links0, d_links_up, d_up_off;
-    DevBuf<signed char> d_levels;
-    DevBuf<unsigned char> d_deleted, d_dirty;
-    DevBuf<long long> d_ids;
+    IndexBuf<float> d_vectors, d_norms;
+    IndexBuf<mn_lo_t> d_vec_lo;    // coded shadow of d_vectors (mn_lo_row_words(ld) dwords per row), grown with it (mn_lo_enabled(ld) only; mn_device.hpp MnLoMeta)
+    IndexBuf<MnLoMeta> d_lo_meta;
+    IndexBuf<int> d_links0, d_links_up, d_up_off;
+    IndexBuf<signed char> d_levels;
+    IndexBuf<unsigned char> d_deleted, d_dirty;
+    IndexBuf<long long> d_ids;
     // host mirror of the link rows (pulled on demand for delete / inspection / load)
     std::vector<int> h_links0, h_links_up;
     bool host_links_valid = true;   // host mirror == device
@@ -112,25 +102,25 @@ struct mn_index : MnStreamEvents {
     std::vector<float> load_vecs;
     int load_first = -1;
     // workspaces
-    DevBuf<unsigned> ws_bm0, ws_bmu;
-    DevBuf<uint2> ws_cand, ws_res;
-    DevBuf<float> ws_q, ws_outd;
-    DevBuf<long long> ws_outi;
-    DevBuf<int> ws_outc, ws_qslots, ws_sel, ws_nsel, ws_upidx;
-    DevBuf<int> lk_target, lk_src, lk_counters, lk_count, lk_fill, lk_binoff, lk_touched, lk_bins, lk_newrows;
-    DevBuf<int> lk_rec, lk_rec_all, lk_cls; // divided link step of the jointly built graph: this rank's records, everybody's, class counts
-    DevBuf<unsigned long long> ws_counters;
-    DevBuf<int> ws_state;
-    DevBuf<int> er_slot, er_level, er_nbr;
-    DevBuf<float> er_dist;
+    IndexBuf<unsigned> ws_bm0, ws_bmu;
+    IndexBuf<uint2> ws_cand, ws_res;
+    IndexBuf<float> ws_q, ws_outd;
+    IndexBuf<long long> ws_outi;
+    IndexBuf<int> ws_outc, ws_qslots, ws_sel, ws_nsel, ws_upidx;
+    IndexBuf<int> lk_target, lk_src, lk_counters, lk_count, lk_fill, lk_binoff, lk_touched, lk_bins, lk_newrows;
+    IndexBuf<int> lk_rec, lk_rec_all, lk_cls; // divided link step of the jointly built graph: this rank's records, everybody's, class counts
+    IndexBuf<unsigned long long> ws_counters;
+    IndexBuf<int> ws_state;
+    IndexBuf<int> er_slot, er_level, er_nbr;
+    IndexBuf<float> er_dist;
     // speculative exact build: read logs of a window's searches, per-row rewrite epochs
-    DevBuf<int> ws_readlog, ws_nread, ws_ncommit, d_stamp0, d_stampU, d_sidx0, d_sidxU, d_saved_rows, d_pre_act, d_pre_cnt, d_pre_row, d_spec_why;
+    IndexBuf<int> ws_readlog, ws_nread, ws_ncommit, d_stamp0, d_stampU, d_sidx0, d_sidxU, d_saved_rows, d_pre_act, d_pre_cnt, d_pre_row, d_spec_why;
     int spec_epoch = 0;
     std::vector<int> staged; // mn_hnsw_batch_stage: slots added but not yet searched / linked
-    DevBuf<int> d_staged;
+    IndexBuf<int> d_staged;
     // multi-GPU exchange buffers (mn_hnsw_build_shared / mn_hnsw_search_sharded)
-    DevBuf<int> sh_sel, sh_nsel, sh_gcnt;
-    DevBuf<int> ws_chlog;            // change log of a single exact insert (mn_hnsw_insert_logged)
+    IndexBuf<int> sh_sel, sh_nsel, sh_gcnt;
+    IndexBuf<int> ws_chlog;            // change log of a single exact insert (mn_hnsw_insert_logged)
     bool want_chlog = false;         // the next run_sequential of one node fills it
     std::vector<int> h_chlog;        // its host copy: [0] entries or -1, then MN_CHLOG_INTS ints each
     // slots whose lists a delete edited: the reference leaves those edits un-persisted (src/hnsw_vtab.c:702-706) until a later
@@ -141,10 +131,10 @@ struct mn_index : MnStreamEvents {
     // the SQL surface's shape: five pageable copies and two synchronisations cost more than the search)
     unsigned char *pin = nullptr;
     size_t pin_cap = 0;
-    DevBuf<unsigned long long> sh_ovf; // [world] heap-workspace overflow counts of the last sharded search, all-gathered
+    IndexBuf<unsigned long long> sh_ovf; // [world] heap-workspace overflow counts of the last sharded search, all-gathered
     int sh_ovf_pending = 0;             // entries of sh_ovf not yet looked at by the host (0: none)
-    DevBuf<long long> sh_gids;
-    DevBuf<float> sh_gd;
+    IndexBuf<long long> sh_gids;
+    IndexBuf<float> sh_gd;
     long long last_spec_searched = 0; // searches the last speculative build ran (≥ nodes inserted)
     bool broken = false; // an insert failed after its kernels had begun to rewrite link rows: nothing can be trusted
     mn_launch_stats last = {0, 0, 0, 0, 0, 0, 0, 0};

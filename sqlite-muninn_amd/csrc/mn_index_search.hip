@@ -353,7 +353,7 @@ extern "C" int mn_hnsw_bruteforce_topk(mn_index *x, const float *d_queries, int6
     if (k <= 16 && nq > 0 && x->n_slots > 0 && !(force && !strcmp(force, "valu"))) {
         int nc = 0, rpc = 0;
         const size_t bytes = mn_brute_mfma_scratch_bytes(v, nq, k, &nc, &rpc);
-        DevBuf<unsigned char> scratch;
+        IndexBuf<unsigned char> scratch;
         if (scratch.reserve(bytes, false, st))
             return -1;
         HIPCHK(hipEventRecord(x->ev0, st));
@@ -483,7 +483,7 @@ static int exact_search_dev(mn_index *x, const float *d_queries, int64_t nq, int
     // one device allocation per call: the pass's scratch | allow bits | marked queries | counters
     const size_t b_mfma = plan.mfma ? mn_exact_mfma_scratch_bytes(v, nq, plan.kp) : 0;
     const size_t b_bits = up256(words * 4), b_marked = up256((size_t)nq * 4);
-    DevBuf<unsigned char> sc;
+    IndexBuf<unsigned char> sc;
     if (sc.reserve(b_mfma + b_bits + b_marked + 256, false, st))
         return -1;
     unsigned *d_allow = reinterpret_cast<unsigned *>(sc.p + b_mfma);
@@ -555,7 +555,7 @@ static int knn_graph_dev(mn_index *x, int k, float r, int64_t *d_ids, float *d_d
                                                 rem ? mn_exact_mfma_scratch_bytes(v, rem, plan.kp, true) : (size_t)0)
                                      : 0;
     const size_t b_xc = plan.mfma ? up256((size_t)n * 8) : 0, b_marked = up256((size_t)B * 4);
-    DevBuf<unsigned char> sc;
+    IndexBuf<unsigned char> sc;
     if (sc.reserve(b_batch + b_xc + b_marked + 256, false, st))
         return -1;
     MnExactSelf self = {0, r, sc.p + b_batch};

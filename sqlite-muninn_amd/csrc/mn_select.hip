@@ -28,8 +28,8 @@
 // other pass of the same expression claims (the two passes of `+x+` share a visited set), so one zero-filled int32[n] serves.
 // An atom under a set operator has no depth map, which makes the reference read every depth as 0: its limit is ignored unless
 // it is 0.  `N+x+M` keeps its own maps and honours its limits everywhere.
-#include "mn_graph_int.hpp"
 #include "mn_guard.hpp"
+#include "mn_prim.hpp"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -44,6 +44,7 @@ typedef unsigned long long sel_u64;
 #define SEL_WAVES (SEL_BLOCK / 64)
 #define SEL_LEVELS_PER_SYNC 16 // measured on a 20 000-node path
 #define SEL_BOTTOM_UP_DIV 16   // auto: bottom-up when the frontier holds more than 1/16 of the direction's list entries
+#define SEL_WHO "mn_graph_select"
 
 // ───────────────────────── parser (host) ─────────────────────────
 // graph_selector_parse.c restated: the same tokens, the same two back-tracking points, the same messages.
@@ -286,27 +287,18 @@ extern "C" int mn_select_parse(const char *expr, mn_select_op **prog, int *n_ops
 enum { SS_CNT0 = 0, SS_LEVELS = 3, SS_BOTTOM_UP = 4, SS_WORDS = 5 };
 
 struct SelWork {
-    size_t words = 0;      // 64-bit words of an n-bit set
-    sel_u64 *sets = nullptr; // [n_sets][words]: the three frontiers, the closure's descendants, then the stack
-    size_t n_sets = 0;
-    int *depth = nullptr;  // [n]
-    unsigned *wcnt = nullptr, *woff = nullptr; // [words + 1] popcounts and their exclusive sums
-    int *o_node = nullptr, *o_depth = nullptr; // [n]
-    sel_u64 *status = nullptr;                 // [SS_WORDS]
-    void *tmp = nullptr;                       // rocPRIM's
-    size_t tmp_bytes = 0;
+    size_t words = 0;           // 64-bit words of an n-bit set
+    DevBuf<sel_u64> sets;       // [sets][words]: the three frontiers, the closure's descendants, then the stack
+    DevBuf<int> depth;          // [n]
+    DevBuf<unsigned> wcnt, woff; // [words + 1] popcounts and their exclusive sums
+    DevBuf<int> o_node, o_depth; // [n]
+    DevBuf<sel_u64> status;     // [SS_WORDS]
+    DevBuf<char> tmp;           // rocPRIM's
     std::vector<int> r_node, r_depth; // the rows of the last call
-    bool ready = false;      // the arrays sized by n alone are allocated
     bool rows_valid = false;
 };
 
-void sel_work_free(SelWork *w) {
-    if (!w)
-        return;
-    (void)hipFree(w->sets); (void)hipFree(w->depth); (void)hipFree(w->wcnt); (void)hipFree(w->woff);
-    (void)hipFree(w->o_node); (void)hipFree(w->o_depth); (void)hipFree(w->status); (void)hipFree(w->tmp);
-    delete w;
-}
+void sel_work_free(SelWork *w) { delete w; }
 
 struct SelLevel {
     int n;
@@ -504,7 +496,7 @@ struct SelRun {
     unsigned bu_div;
     int64_t levels = 0, launches = 0, syncs = 0, bottom_up = 0;
     double device_ms = 0;
-    sel_u64 *set(size_t i) const { return w->sets + i * w->words; }
+    sel_u64 *set(size_t i) const { return w->sets.p + i * w->words; }
 };
 
 enum { SET_F0 = 0, SET_DESC = 3, SET_STACK = 4 };
@@ -530,7 +522,7 @@ int sel_reach(SelRun &r, sel_u64 *visited, const sel_u64 *seeds, int seed, bool 
     a.otgt = forward ? g->tgt_in : g->tgt_out;
     a.visited = visited;
     a.status = w->status;
-    a.depth = tracked ? w->depth : nullptr;
+    a.depth = tracked ? w->depth.p : nullptr;
     a.mode = r.mode;
     a.entries_dir = (sel_u64)(forward ? g->e_out : g->e_in);
     a.bu_div = r.bu_div;
@@ -547,27 +539,20 @@ int sel_reach(SelRun &r, sel_u64 *visited, const sel_u64 *seeds, int seed, bool 
             hipLaunchKernelGGL(k_sel_level, dim3(sel_wave_grid(words)), dim3(SEL_BLOCK), 0, r.st, a);
         }
         r.launches += G;
-        GCHK(hipEventRecord(g->ev1, r.st));
-        GCHK(hipGetLastError());
+        if (graph_mark(g))
+            return -1;
         GCHK(hipMemcpyAsync(h, w->status, sizeof(h), hipMemcpyDeviceToHost, r.st)); // the group's one round trip
-        GCHK(hipStreamSynchronize(r.st));
+        if (graph_wait(g, &r.device_ms))
+            return -1;
         r.syncs++;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-            r.device_ms += ms;
         GCHK(hipEventRecord(g->ev0, r.st));
         if (h[SS_CNT0 + (L - 1) % 3] == 0) // the last level queued found nothing that has a list
             break;
     }
     r.levels += (int64_t)h[SS_LEVELS];
     r.bottom_up += (int64_t)h[SS_BOTTOM_UP];
-    if (L == 1) { // no level was queued: the seeding alone
-        GCHK(hipEventRecord(g->ev1, r.st));
-        GCHK(hipStreamSynchronize(r.st));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-            r.device_ms += ms;
-    }
+    if (L == 1) // no level was queued: the seeding alone
+        return graph_mark_wait(g, &r.device_ms);
     return 0;
 }
 
@@ -643,35 +628,18 @@ extern "C" int64_t mn_graph_select(mn_graph *g, const mn_select_op *prog, int n_
     g->last_ms = 0;
     hipStream_t st = g->stream;
     const size_t words = ((size_t)N + 63) / 64;
-    if (!w->ready) { // all of the fixed part or none of it: a later call must not find half
-        w->words = words;
-        const bool ok = hipMalloc(&w->depth, (size_t)N * sizeof(int)) == hipSuccess && hipMalloc(&w->o_node, (size_t)N * sizeof(int)) == hipSuccess &&
-                        hipMalloc(&w->o_depth, (size_t)N * sizeof(int)) == hipSuccess &&
-                        hipMalloc(&w->wcnt, (words + 1) * sizeof(unsigned)) == hipSuccess &&
-                        hipMalloc(&w->woff, (words + 1) * sizeof(unsigned)) == hipSuccess &&
-                        hipMalloc(&w->status, SS_WORDS * sizeof(sel_u64)) == hipSuccess;
-        if (!ok) {
-            (void)hipFree(w->depth); (void)hipFree(w->o_node); (void)hipFree(w->o_depth); (void)hipFree(w->wcnt); (void)hipFree(w->woff);
-            (void)hipFree(w->status);
-            w->depth = w->o_node = w->o_depth = nullptr;
-            w->wcnt = w->woff = nullptr;
-            w->status = nullptr;
-            gset_err("mn_graph_select: out of device memory (N = %d)", N);
-            return -1;
-        }
-        w->ready = true;
+    w->words = words;
+    // the arrays sized by n alone: those a failed call left in place are found again by the next
+    if (w->depth.fit(gset_err, SEL_WHO, (size_t)N) || w->o_node.fit(gset_err, SEL_WHO, (size_t)N) ||
+        w->o_depth.fit(gset_err, SEL_WHO, (size_t)N) || w->wcnt.fit(gset_err, SEL_WHO, words + 1) ||
+        w->woff.fit(gset_err, SEL_WHO, words + 1) || w->status.fit(gset_err, SEL_WHO, SS_WORDS)) {
+        gset_err("mn_graph_select: out of device memory (N = %d)", N);
+        return -1;
     }
     const size_t need_sets = SET_STACK + (size_t)max_sp;
-    if (w->n_sets < need_sets) {
-        GCHK(hipStreamSynchronize(st));
-        (void)hipFree(w->sets);
-        w->sets = nullptr;
-        w->n_sets = 0;
-        if (hipMalloc(&w->sets, need_sets * words * sizeof(sel_u64)) != hipSuccess) {
-            gset_err("mn_graph_select: out of device memory (%zu sets of %d bits)", need_sets, N);
-            return -1;
-        }
-        w->n_sets = need_sets;
+    if (w->sets.fit(gset_err, SEL_WHO, need_sets * words)) {
+        gset_err("mn_graph_select: out of device memory (%zu sets of %d bits)", need_sets, N);
+        return -1;
     }
     SelRun r;
     r.g = g;
@@ -745,33 +713,18 @@ extern "C" int64_t mn_graph_select(mn_graph *g, const mn_select_op *prog, int n_
     GCHK(hipEventRecord(g->ev0, st));
     hipLaunchKernelGGL(k_sel_popcount, dim3((unsigned)((words + 1 + SEL_BLOCK - 1) / SEL_BLOCK)), dim3(SEL_BLOCK), 0, st, (unsigned)words,
                        result, w->wcnt);
-    size_t need = 0;
-    if (rocprim::exclusive_scan(nullptr, need, w->wcnt, w->woff, 0u, words + 1, rocprim::plus<unsigned>(), st) != hipSuccess) {
-        gset_err("rocprim::exclusive_scan (size query) failed");
+    if (prim_run(SEL_WHO, "rocprim::exclusive_scan", w->tmp, st, [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, w->wcnt.p, w->woff.p, 0u, words + 1, rocprim::plus<unsigned>(), st);
+        }))
         return -1;
-    }
-    if (need > w->tmp_bytes) {
-        GCHK(hipStreamSynchronize(st));
-        (void)hipFree(w->tmp);
-        w->tmp = nullptr;
-        w->tmp_bytes = 0;
-        if (hipMalloc(&w->tmp, need) != hipSuccess) {
-            gset_err("mn_graph_select: out of device memory (%zu bytes)", need);
-            return -1;
-        }
-        w->tmp_bytes = need;
-    }
-    if (rocprim::exclusive_scan(w->tmp, need, w->wcnt, w->woff, 0u, words + 1, rocprim::plus<unsigned>(), st) != hipSuccess) {
-        gset_err("rocprim::exclusive_scan failed");
-        return -1;
-    }
     hipLaunchKernelGGL(k_sel_emit, dim3(sel_wave_grid(words)), dim3(SEL_BLOCK), 0, st, (unsigned)words, result, w->woff, w->depth, w->o_node,
                        w->o_depth);
-    GCHK(hipEventRecord(g->ev1, st));
-    GCHK(hipGetLastError());
+    if (graph_mark(g))
+        return -1;
     unsigned total = 0;
-    GCHK(hipMemcpyAsync(&total, w->woff + words, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
+    GCHK(hipMemcpyAsync(&total, w->woff.p + words, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (graph_wait(g, &r.device_ms))
+        return -1;
     if (total > (unsigned)N) {
         gset_err("mn_graph_select: %u rows from %d nodes", total, N);
         return -1;
@@ -783,9 +736,6 @@ extern "C" int64_t mn_graph_select(mn_graph *g, const mn_select_op *prog, int n_
         GCHK(hipMemcpyAsync(w->r_depth.data(), w->o_depth, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, st));
         GCHK(hipStreamSynchronize(st));
     }
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess)
-        r.device_ms += ms;
     g->last_ms = r.device_ms;
     if (stats) {
         stats->rows = total;

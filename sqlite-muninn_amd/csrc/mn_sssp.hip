@@ -444,11 +444,6 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_fast_trace(int P, DevGraph g, c
 
 // ───────────────────────── host ─────────────────────────
 
-static unsigned sp_grid(sp_u64 items, unsigned per_block, unsigned max_blocks) {
-    const sp_u64 b = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<sp_u64>(1, std::min<sp_u64>(b, max_blocks));
-}
-
 struct SpRun { // what the three procedures share: the rows as they come, and where each pair's stand
     mn_graph *g;
     int64_t n_pairs;
@@ -461,14 +456,10 @@ struct SpRun { // what the three procedures share: the rows as they come, and wh
     hipStream_t stream() const { return g->stream; }
 };
 
-// ev0 .. ev1 around the launches since the last wait, then the wait
+// ev0 .. ev1 around the launches since the last wait, then the wait, and ev0 again for those that follow
 static int sp_wait(SpRun &r) {
-    GCHK(hipEventRecord(r.g->ev1, r.stream()));
-    GCHK(hipGetLastError());
-    GCHK(hipStreamSynchronize(r.stream()));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, r.g->ev0, r.g->ev1) == hipSuccess)
-        r.ms += ms;
+    if (graph_mark_wait(r.g, &r.ms))
+        return -1;
     GCHK(hipEventRecord(r.g->ev0, r.stream()));
     return 0;
 }
@@ -486,7 +477,7 @@ static int sp_scan_weights(mn_graph *g, SpWork *w) {
     GCHK(hipMemsetAsync(d_out, 0, 4 * sizeof(sp_u64), g->stream));
     GCHK(hipMemsetAsync(d_sum, 0, sizeof(double), g->stream));
     if (g->e_out > 0)
-        hipLaunchKernelGGL(k_sp_wscan, dim3(sp_grid((sp_u64)g->e_out, SP_BLOCK * 8, 1024)), dim3(SP_BLOCK), 0, g->stream, g->e_out,
+        hipLaunchKernelGGL(k_sp_wscan, dim3(launch_blocks((sp_u64)g->e_out, SP_BLOCK * 8, 1024)), dim3(SP_BLOCK), 0, g->stream, g->e_out,
                            g->w_out, d_out, d_sum);
     GCHK(hipGetLastError());
     sp_u64 h[4];
@@ -548,8 +539,7 @@ static int sp_replay(SpRun &r) {
     hipStream_t st = r.stream();
     const size_t Q = (size_t)g->e_out + 1;
     const size_t per_pair = SP_REPLAY_BYTES_PER_ENTRY * Q + SP_REPLAY_BYTES_PER_NODE * (size_t)N;
-    const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)r.n_pairs, scratch_budget("MN_SP_SCRATCH_MB", 0) / per_pair,
-                                                           (size_t)0x7fffffff}));
+    const size_t P = scratch_chunk((size_t)r.n_pairs, scratch_budget("MN_SP_SCRATCH_MB", 0), per_pair, (size_t)0x7fffffff);
     DevArena scr;
     ReplayArgs a;
     memset(&a, 0, sizeof(a));
@@ -582,7 +572,7 @@ static int sp_replay(SpRun &r) {
         hipLaunchKernelGGL(k_sp_replay, dim3(Pc), dim3(SP_WAVE), 0, st, a);
         const ReplayArgs &ca = a;
         if (sp_take_rows(r, Pc, a.cnt, nullptr, p0, [&](const long long *row0, int *o_node, double *o_dist) {
-                hipLaunchKernelGGL(k_sp_replay_trace, dim3(sp_grid((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), dim3(SP_BLOCK), 0, st, Pc, N,
+                hipLaunchKernelGGL(k_sp_replay_trace, dim3(launch_blocks((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), dim3(SP_BLOCK), 0, st, Pc, N,
                                    ca.end, ca.cnt, row0, ca.s_dist, ca.s_par, o_node, o_dist);
             }))
             return -1;
@@ -638,7 +628,7 @@ static int sp_fast(SpRun &r, const SpWork *w) {
     const size_t D = slot_start.size();
     r.st.sources = (int)D;
     const size_t per_slot = SP_FAST_BYTES_PER_NODE_SLOT * (size_t)N;
-    const size_t S = std::max<size_t>(1, std::min<size_t>({D, scratch_budget("MN_SP_SCRATCH_MB", 0) / per_slot, (size_t)0x7fffffff / (size_t)N}));
+    const size_t S = scratch_chunk(D, scratch_budget("MN_SP_SCRATCH_MB", 0), per_slot, (size_t)0x7fffffff / (size_t)N);
     const sp_u64 cap = (sp_u64)S * (sp_u64)N;
     DevArena scr;
     FastArgs a;
@@ -695,13 +685,13 @@ static int sp_fast(SpRun &r, const SpWork *w) {
         GCHK(hipMemcpyAsync(d_pend, pair_end.data() + i0, (size_t)Pc * sizeof(int), hipMemcpyHostToDevice, st));
         GCHK(hipMemcpyAsync(d_pslot, h_slot.data(), (size_t)Pc * sizeof(int), hipMemcpyHostToDevice, st));
         const sp_u64 total = (sp_u64)Sc * (sp_u64)N;
-        const dim3 grid_all(sp_grid(total, SP_BLOCK * 4, 8192)), grid_s(sp_grid((sp_u64)Sc, SP_BLOCK, 0x7fffffffu)), blk(SP_BLOCK);
+        const dim3 grid_all(launch_blocks(total, SP_BLOCK * 4, 8192)), grid_s(launch_blocks((sp_u64)Sc, SP_BLOCK, 0x7fffffffu)), blk(SP_BLOCK);
         hipLaunchKernelGGL(k_sssp_init, grid_all, blk, 0, st, total, a.dist, a.stamp, a.key);
         hipLaunchKernelGGL(k_sssp_seed, grid_s, blk, 0, st, Sc, a, qa);
         sp_u64 *cur = qa, *next = qb, ncur = (sp_u64)Sc;
         for (unsigned pass = 1; pass < SP_FAR - 1; pass++) {
             GCHK(hipMemsetAsync(a.ctr, 0, sizeof(sp_u64), st));
-            hipLaunchKernelGGL(k_sssp_relax, dim3(sp_grid(ncur, SP_BLOCK / SP_WAVE, 8192)), blk, 0, st, a, cur, ncur, next, pass + 1);
+            hipLaunchKernelGGL(k_sssp_relax, dim3(launch_blocks(ncur, SP_BLOCK / SP_WAVE, 8192)), blk, 0, st, a, cur, ncur, next, pass + 1);
             if (read_ctr())
                 return -1;
             r.st.passes++;
@@ -730,7 +720,7 @@ static int sp_fast(SpRun &r, const SpWork *w) {
         ncur = (sp_u64)Sc;
         for (unsigned level = 0; level < 0x7FFFFFFEu && ncur > 0; level++) {
             GCHK(hipMemsetAsync(a.ctr, 0, sizeof(sp_u64), st));
-            hipLaunchKernelGGL(k_tight_level, dim3(sp_grid(ncur, SP_BLOCK / SP_WAVE, 8192)), blk, 0, st, a, cur, ncur, next, level);
+            hipLaunchKernelGGL(k_tight_level, dim3(launch_blocks(ncur, SP_BLOCK / SP_WAVE, 8192)), blk, 0, st, a, cur, ncur, next, level);
             if (read_ctr())
                 return -1;
             if (h_ctr[2]) {
@@ -740,10 +730,10 @@ static int sp_fast(SpRun &r, const SpWork *w) {
             std::swap(cur, next);
             ncur = h_ctr[0];
         }
-        hipLaunchKernelGGL(k_sp_fast_count, dim3(sp_grid((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), blk, 0, st, Pc, N, d_pslot, d_pend, a.key, d_cnt);
+        hipLaunchKernelGGL(k_sp_fast_count, dim3(launch_blocks((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), blk, 0, st, Pc, N, d_pslot, d_pend, a.key, d_cnt);
         const FastArgs &ca = a;
         if (sp_take_rows(r, Pc, d_cnt, order.data() + i0, 0, [&](const long long *row0, int *o_node, double *o_dist) {
-                hipLaunchKernelGGL(k_sp_fast_trace, dim3(sp_grid((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), blk, 0, st, Pc, ca.g, d_pslot, d_pend,
+                hipLaunchKernelGGL(k_sp_fast_trace, dim3(launch_blocks((sp_u64)Pc, SP_BLOCK, 0x7fffffffu)), blk, 0, st, Pc, ca.g, d_pslot, d_pend,
                                    d_cnt, row0, ca.dist, ca.key, o_node, o_dist);
             }))
             return -1;

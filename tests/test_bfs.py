@@ -181,6 +181,26 @@ def test_weights_are_ignored(gpu, random3000):
     gw.close()
 
 
+def test_pool_grows_in_the_middle_of_a_traversal(random3000, monkeypatch):
+    """450 seeds in one chunk whose rows outnumber the pool's first allocation, so the pool is grown between two levels
+    with the rows so far kept.  That rests on mn_bfs.hip's first pool size, min(S * N, max(64 * S, 2^20)) entries: 2^20 here,
+    where S * N is 1 350 000 and no earlier call on this handle has had more than a few seeds.  The same seeds 100 to a
+    chunk (300 000 entries: no growth) give the same rows."""
+    g, lists, _ = random3000
+    seeds = list(range(0, 2700, 6))
+    assert len(seeds) == 450
+    monkeypatch.delenv("MN_BFS_SCRATCH_MB", raising=False)
+    whole = check(g, lists, seeds, UNLIMITED, "both")
+    stats = g.bfs_stats
+    print("pool growth: chunks", stats["chunks"], "rows", stats["rows"], "levels", stats["levels"])
+    assert stats["chunks"] == 1
+    assert stats["rows"] > 2**20
+    monkeypatch.setenv("MN_BFS_SCRATCH_MB", repr((100 + 0.5) * 64 * 3000 / 2**20))
+    parts = g.bfs_batch(seeds, UNLIMITED, "both")
+    assert g.bfs_stats["chunks"] == 5
+    assert all(np.array_equal(a, b) for a, b in zip(whole, parts))
+
+
 # ───────────────────────── batches ─────────────────────────
 
 @pytest.fixture(scope="module")
