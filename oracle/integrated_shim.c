@@ -3,7 +3,7 @@
  * Evidence for SURVEY §8(b) "the other graph_* surface remains loadable": the reference's UNMODIFIED entry point
  * (src/muninn.c) and its UNMODIFIED non-hot translation units (graph_tvf, graph_centrality, graph_adjacency, graph_csr,
  * graph_load, graph_select*, id_validate — compiled where they lie) are linked into one muninn.so together with this
- * repository's re-pointed hot-path files (ext/mn_vtab_hnsw.c, ext/mn_graph_sql.c, ext/mn_graph_tvf.c, ext/mn_tvf.c over
+ * repository's re-pointed hot-path files (ext/mn_vtab_hnsw.c, ext/mn_hnsw_tvf.c, ext/mn_graph_sql.c, ext/mn_graph_tvf.c, ext/mn_tvf.c over
  * libmuninn_hip.so).  The reference's hnsw_vtab.c / hnsw_algo.c / vec_math.c / priority_queue.c / node2vec.c /
  * graph_community.c are NOT in the link.  This file only supplies the three registration functions muninn.c calls for
  * them, forwarding to this repository's registrations.  Nothing built here travels to the GPU box or ships. */

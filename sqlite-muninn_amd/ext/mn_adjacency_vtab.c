@@ -21,6 +21,7 @@
 #include "../../include/muninn_hip.h"
 #include "mn_nodemap.h"
 #include "mn_sqlite_abi.h"
+#include "mn_tvf.h" /* mn_sql_exec_owned, mn_sql_prepare_owned */
 
 #include <pthread.h>
 #include <stdint.h>
@@ -266,27 +267,10 @@ void mn_adj_resident_offer(sqlite3 *db, const char *name, mn_graph *g, char *con
     entry_set(db, name, g, ids, n, cfg_int(db, name, "generation", -1));
 }
 
-/* ───────────────────────── small SQL helpers ───────────────────────── */
-
-static int exec_free(sqlite3 *db, char *sql) {
-    if (!sql)
-        return SQLITE_NOMEM;
-    int rc = sqlite3_exec(db, sql, 0, 0, 0);
-    sqlite3_free(sql);
-    return rc;
-}
-
-static int prepare_free(sqlite3 *db, char *sql, sqlite3_stmt **st) {
-    *st = 0;
-    if (!sql)
-        return SQLITE_NOMEM;
-    int rc = sqlite3_prepare_v2(db, sql, -1, st, 0);
-    sqlite3_free(sql);
-    return rc;
-}
+/* ───────────────────────── small SQL helpers (statements: mn_sql_exec_owned, mn_sql_prepare_owned of mn_tvf.h) ───────────────────────── */
 
 static int cfg_set(sqlite3 *db, const char *name, const char *key, const char *value) { /* :275-281 */
-    return exec_free(db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\"(key, value) VALUES ('%w', '%w')", name, key, value));
+    return mn_sql_exec_owned(db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\"(key, value) VALUES ('%w', '%w')", name, key, value));
 }
 
 static int cfg_set_int(sqlite3 *db, const char *name, const char *key, sqlite3_int64 v) {
@@ -297,7 +281,7 @@ static int cfg_set_int(sqlite3 *db, const char *name, const char *key, sqlite3_i
 
 static sqlite3_int64 cfg_int(sqlite3 *db, const char *name, const char *key, sqlite3_int64 dflt) { /* :289-305: atoll of the text */
     sqlite3_stmt *st;
-    if (prepare_free(db, sqlite3_mprintf("SELECT value FROM \"%w_config\" WHERE key='%w'", name, key), &st) != SQLITE_OK)
+    if (mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT value FROM \"%w_config\" WHERE key='%w'", name, key), &st) != SQLITE_OK)
         return dflt;
     sqlite3_int64 out = dflt;
     if (sqlite3_step(st) == SQLITE_ROW) {
@@ -311,7 +295,7 @@ static sqlite3_int64 cfg_int(sqlite3 *db, const char *name, const char *key, sql
 
 static sqlite3_int64 delta_rows(sqlite3 *db, const char *name) {
     sqlite3_stmt *st;
-    if (prepare_free(db, sqlite3_mprintf("SELECT COUNT(*) FROM \"%w_delta\"", name), &st) != SQLITE_OK)
+    if (mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT COUNT(*) FROM \"%w_delta\"", name), &st) != SQLITE_OK)
         return 0;
     sqlite3_int64 n = sqlite3_step(st) == SQLITE_ROW ? sqlite3_column_int64(st, 0) : 0;
     sqlite3_finalize(st);
@@ -384,7 +368,7 @@ static int create_shadows(sqlite3 *db, const char *name) {
         "(rowid INTEGER PRIMARY KEY, src TEXT, dst TEXT, weight REAL, op INTEGER)",
     };
     for (int i = 0; i < 6; i++) {
-        int rc = exec_free(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w%s\" %s", name, SHADOWS[i], cols[i]));
+        int rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w%s\" %s", name, SHADOWS[i], cols[i]));
         if (rc != SQLITE_OK)
             return rc;
     }
@@ -393,35 +377,35 @@ static int create_shadows(sqlite3 *db, const char *name) {
 
 static void drop_shadows(sqlite3 *db, const char *name) {
     for (int i = 0; i < 6; i++)
-        exec_free(db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w%s\"", name, SHADOWS[i]));
+        mn_sql_exec_owned(db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w%s\"", name, SHADOWS[i]));
 }
 
 static int install_triggers(sqlite3 *db, const AdjTab *t, const char *name) {
     const char *w = t->weight_col ? t->weight_col : "NULL"; /* the quirk: NEW."NULL" (:227) */
-    int rc = exec_free(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_ai\" AFTER INSERT ON \"%w\" BEGIN "
-                                           "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
-                                           "VALUES (NEW.\"%w\", NEW.\"%w\", NEW.\"%w\", 1); END",
-                                           name, t->edge_table, name, t->src_col, t->dst_col, w));
+    int rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_ai\" AFTER INSERT ON \"%w\" BEGIN "
+                                                   "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
+                                                   "VALUES (NEW.\"%w\", NEW.\"%w\", NEW.\"%w\", 1); END",
+                                                   name, t->edge_table, name, t->src_col, t->dst_col, w));
     if (rc != SQLITE_OK)
         return rc;
-    rc = exec_free(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_ad\" AFTER DELETE ON \"%w\" BEGIN "
-                                       "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
-                                       "VALUES (OLD.\"%w\", OLD.\"%w\", OLD.\"%w\", 2); END",
-                                       name, t->edge_table, name, t->src_col, t->dst_col, w));
+    rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_ad\" AFTER DELETE ON \"%w\" BEGIN "
+                                               "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
+                                               "VALUES (OLD.\"%w\", OLD.\"%w\", OLD.\"%w\", 2); END",
+                                               name, t->edge_table, name, t->src_col, t->dst_col, w));
     if (rc != SQLITE_OK)
         return rc;
-    return exec_free(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_au\" AFTER UPDATE ON \"%w\" BEGIN "
-                                         "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
-                                         "VALUES (OLD.\"%w\", OLD.\"%w\", OLD.\"%w\", 2); "
-                                         "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
-                                         "VALUES (NEW.\"%w\", NEW.\"%w\", NEW.\"%w\", 1); END",
-                                         name, t->edge_table, name, t->src_col, t->dst_col, w, name, t->src_col, t->dst_col, w));
+    return mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TRIGGER IF NOT EXISTS \"%w_au\" AFTER UPDATE ON \"%w\" BEGIN "
+                                                 "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
+                                                 "VALUES (OLD.\"%w\", OLD.\"%w\", OLD.\"%w\", 2); "
+                                                 "INSERT INTO \"%w_delta\"(src, dst, weight, op) "
+                                                 "VALUES (NEW.\"%w\", NEW.\"%w\", NEW.\"%w\", 1); END",
+                                                 name, t->edge_table, name, t->src_col, t->dst_col, w, name, t->src_col, t->dst_col, w));
 }
 
 static void remove_triggers(sqlite3 *db, const char *name) {
     static const char *const suffix[3] = {"_ai", "_ad", "_au"};
     for (int i = 0; i < 3; i++)
-        exec_free(db, sqlite3_mprintf("DROP TRIGGER IF EXISTS \"%w%s\"", name, suffix[i]));
+        mn_sql_exec_owned(db, sqlite3_mprintf("DROP TRIGGER IF EXISTS \"%w%s\"", name, suffix[i]));
 }
 
 /* ───────────────────────── stored blocks (:342-446) ───────────────────────── */
@@ -429,8 +413,8 @@ static void remove_triggers(sqlite3 *db, const char *name) {
 static int store_block(sqlite3 *db, const char *name, const char *suffix, int block_id, const int32_t *off, int nodes,
                        const int32_t *tgt, const double *w, int edges) {
     sqlite3_stmt *st;
-    int rc = prepare_free(db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w%s\"(block_id, offsets, targets, weights) VALUES (?, ?, ?, ?)",
-                                              name, suffix), &st);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w%s\"(block_id, offsets, targets, weights) VALUES (?, ?, ?, ?)",
+                                                      name, suffix), &st);
     if (rc != SQLITE_OK)
         return rc;
     sqlite3_bind_int(st, 1, block_id);
@@ -451,7 +435,7 @@ static int store_block(sqlite3 *db, const char *name, const char *suffix, int bl
 /* a whole CSR as rows of ADJ_BLOCK nodes: offsets rebased to the block's first entry, targets as they are (:380-416) */
 static int store_blocks(sqlite3 *db, const char *name, const char *suffix, int n, const int32_t *off, const int32_t *tgt,
                         const double *w) {
-    exec_free(db, sqlite3_mprintf("DELETE FROM \"%w%s\"", name, suffix));
+    mn_sql_exec_owned(db, sqlite3_mprintf("DELETE FROM \"%w%s\"", name, suffix));
     if (n <= 0) {
         const int32_t zero = 0;
         return store_block(db, name, suffix, 0, &zero, 0, 0, 0, 0);
@@ -475,7 +459,7 @@ static int store_blocks(sqlite3 *db, const char *name, const char *suffix, int n
 static int load_block(sqlite3 *db, const char *name, const char *suffix, int block_id, CsrArray *c) {
     memset(c, 0, sizeof(*c));
     sqlite3_stmt *st;
-    int rc = prepare_free(db, sqlite3_mprintf("SELECT offsets, targets, weights FROM \"%w%s\" WHERE block_id=?", name, suffix), &st);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT offsets, targets, weights FROM \"%w%s\" WHERE block_id=?", name, suffix), &st);
     if (rc != SQLITE_OK)
         return rc;
     sqlite3_bind_int(st, 1, block_id);
@@ -569,9 +553,9 @@ static int load_all_blocks(sqlite3 *db, const char *name, const char *suffix, in
 /* ───────────────────────── node registry and degrees (:488-559) ───────────────────────── */
 
 static int store_nodes(sqlite3 *db, const char *name, char *const *ids, int n) {
-    exec_free(db, sqlite3_mprintf("DELETE FROM \"%w_nodes\"", name));
+    mn_sql_exec_owned(db, sqlite3_mprintf("DELETE FROM \"%w_nodes\"", name));
     sqlite3_stmt *st;
-    int rc = prepare_free(db, sqlite3_mprintf("INSERT INTO \"%w_nodes\"(idx, id) VALUES (?, ?)", name), &st);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("INSERT INTO \"%w_nodes\"(idx, id) VALUES (?, ?)", name), &st);
     if (rc != SQLITE_OK)
         return rc;
     for (int i = 0; i < n; i++) {
@@ -587,10 +571,10 @@ static int store_nodes(sqlite3 *db, const char *name, char *const *ids, int n) {
 /* counts from the offsets; the weighted sums are the caller's (list-order f64 sums, or the counts where there are no weights) */
 static int store_degrees(sqlite3 *db, const char *name, int n, const int32_t *off_out, const int32_t *off_in, const double *w_in,
                          const double *w_out) {
-    exec_free(db, sqlite3_mprintf("DELETE FROM \"%w_degree\"", name));
+    mn_sql_exec_owned(db, sqlite3_mprintf("DELETE FROM \"%w_degree\"", name));
     sqlite3_stmt *st;
-    int rc = prepare_free(db, sqlite3_mprintf("INSERT INTO \"%w_degree\"(idx, in_deg, out_deg, w_in_deg, w_out_deg) VALUES (?, ?, ?, ?, ?)",
-                                              name), &st);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("INSERT INTO \"%w_degree\"(idx, in_deg, out_deg, w_in_deg, w_out_deg) VALUES (?, ?, ?, ?, ?)",
+                                                      name), &st);
     if (rc != SQLITE_OK)
         return rc;
     for (int i = 0; i < n; i++) {
@@ -651,9 +635,9 @@ static int full_rebuild(AdjTab *t) {
         return SQLITE_ERROR;
     }
     sqlite3_stmt *st;
-    int rc = prepare_free(db, with_w ? sqlite3_mprintf("SELECT \"%w\", \"%w\", \"%w\" FROM \"%w\"", t->src_col, t->dst_col, t->weight_col,
-                                                       t->edge_table)
-                                     : sqlite3_mprintf("SELECT \"%w\", \"%w\" FROM \"%w\"", t->src_col, t->dst_col, t->edge_table), &st);
+    int rc = mn_sql_prepare_owned(db, with_w ? sqlite3_mprintf("SELECT \"%w\", \"%w\", \"%w\" FROM \"%w\"", t->src_col, t->dst_col, t->weight_col,
+                                                               t->edge_table)
+                                             : sqlite3_mprintf("SELECT \"%w\", \"%w\" FROM \"%w\"", t->src_col, t->dst_col, t->edge_table), &st);
     if (rc != SQLITE_OK) {
         t->base.zErrMsg = sqlite3_mprintf("failed to prepare: %s", sqlite3_errmsg(db));
         return rc;
@@ -725,7 +709,7 @@ static int full_rebuild(AdjTab *t) {
             cfg_set_int(db, t->name, "node_count", n);
             cfg_set_int(db, t->name, "edge_count", rows.n);
             cfg_set_int(db, t->name, "block_size", ADJ_BLOCK);
-            exec_free(db, sqlite3_mprintf("DELETE FROM \"%w_delta\"", t->name));
+            mn_sql_exec_owned(db, sqlite3_mprintf("DELETE FROM \"%w_delta\"", t->name));
         } else {
             sqlite3_exec(db, "ROLLBACK TO adj_rebuild", 0, 0, 0);
         }
@@ -836,7 +820,7 @@ static int incremental_rebuild(AdjTab *t) {
     NodeMap nm;
     nm_init(&nm);
     sqlite3_stmt *st;
-    int rc = prepare_free(db, sqlite3_mprintf("SELECT idx, id FROM \"%w_nodes\" ORDER BY idx", t->name), &st);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT idx, id FROM \"%w_nodes\" ORDER BY idx", t->name), &st);
     if (rc != SQLITE_OK) {
         nm_free(&nm);
         return rc;
@@ -847,7 +831,7 @@ static int incremental_rebuild(AdjTab *t) {
             nm_get(&nm, id);
     }
     sqlite3_finalize(st);
-    rc = prepare_free(db, sqlite3_mprintf("SELECT src, dst, weight, op FROM \"%w_delta\"", t->name), &st);
+    rc = mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT src, dst, weight, op FROM \"%w_delta\"", t->name), &st);
     if (rc != SQLITE_OK) {
         nm_free(&nm);
         return rc;
@@ -937,7 +921,7 @@ static int incremental_rebuild(AdjTab *t) {
             for (int i = 0; i < nd; i++)
                 net += fwd[i].op == 1 ? 1 : -1;
             cfg_set_int(db, t->name, "edge_count", cfg_int(db, t->name, "edge_count", 0) + net);
-            exec_free(db, sqlite3_mprintf("DELETE FROM \"%w_delta\"", t->name));
+            mn_sql_exec_owned(db, sqlite3_mprintf("DELETE FROM \"%w_delta\"", t->name));
         } else {
             sqlite3_exec(db, "ROLLBACK TO adj_incr", 0, 0, 0);
             full = rc == -1;
@@ -1101,10 +1085,10 @@ static int adj_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, 
     if (rc != SQLITE_OK)
         return rc;
     const int point = idxNum == 1 && argc >= 1;
-    rc = prepare_free(t->db, sqlite3_mprintf("SELECT n.idx, n.id, COALESCE(d.in_deg, 0), COALESCE(d.out_deg, 0), "
-                                             "COALESCE(d.w_in_deg, 0.0), COALESCE(d.w_out_deg, 0.0) "
-                                             "FROM \"%w_nodes\" n LEFT JOIN \"%w_degree\" d ON n.idx = d.idx %s",
-                                             t->name, t->name, point ? "WHERE n.id = ?" : "ORDER BY n.idx"), &c->st);
+    rc = mn_sql_prepare_owned(t->db, sqlite3_mprintf("SELECT n.idx, n.id, COALESCE(d.in_deg, 0), COALESCE(d.out_deg, 0), "
+                                                     "COALESCE(d.w_in_deg, 0.0), COALESCE(d.w_out_deg, 0.0) "
+                                                     "FROM \"%w_nodes\" n LEFT JOIN \"%w_degree\" d ON n.idx = d.idx %s",
+                                                     t->name, t->name, point ? "WHERE n.id = ?" : "ORDER BY n.idx"), &c->st);
     if (rc != SQLITE_OK)
         return rc;
     if (point)
@@ -1174,7 +1158,7 @@ static int adj_update(sqlite3_vtab *v, int argc, sqlite3_value **argv, sqlite3_i
 static int adj_rename(sqlite3_vtab *v, const char *to) { /* :1373-1397 */
     AdjTab *t = (AdjTab *)v;
     for (int i = 0; i < 6; i++) {
-        int rc = exec_free(t->db, sqlite3_mprintf("ALTER TABLE \"%w%s\" RENAME TO \"%w%s\"", t->name, SHADOWS[i], to, SHADOWS[i]));
+        int rc = mn_sql_exec_owned(t->db, sqlite3_mprintf("ALTER TABLE \"%w%s\" RENAME TO \"%w%s\"", t->name, SHADOWS[i], to, SHADOWS[i]));
         if (rc != SQLITE_OK)
             return rc;
     }

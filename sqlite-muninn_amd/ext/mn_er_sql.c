@@ -29,6 +29,7 @@
 #include "../../include/muninn_hip.h"
 #include "mn_nodemap.h"
 #include "mn_sqlite_abi.h"
+#include "mn_vtab_hnsw.h"
 
 #include <math.h>
 
@@ -38,9 +39,6 @@
  * scripts/gen_er_golden.py measures it into tests/golden/er.json.gz and tests/test_er_sql.py compares. */
 #define MN_ER_SLOT_result_subtype 209
 #define sqlite3_result_subtype MN_API(MN_ER_SLOT_result_subtype, void (*)(sqlite3_context *, unsigned int))
-
-/* mn_vtab_hnsw.c */
-mn_index *mn_vtab_hnsw_index_of(sqlite3 *db, const char *table, char **err);
 
 typedef struct {
     char *p;
@@ -274,7 +272,7 @@ static void fn_extract_er(sqlite3_context *ctx, int argc, sqlite3_value **argv) 
     int64_t n_edges = 0;
     {
         char *ierr = 0;
-        mn_index *idx = mn_vtab_hnsw_index_of(db, hnsw_table, &ierr);
+        mn_index *idx = mn_vtab_hnsw_index_of(db, hnsw_table, 0, &ierr);
         if (!idx) {
             err = sqlite3_mprintf("muninn_extract_er: %s", ierr ? ierr : "no index");
             sqlite3_free(ierr);

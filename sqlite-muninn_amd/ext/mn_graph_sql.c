@@ -9,6 +9,7 @@
  * compute is mn_node2vec_train / mn_graph_leiden.
  */
 #include "mn_tvf.h"
+#include "mn_vtab_hnsw.h" /* node2vec_train's output step straight into a live hnsw_index */
 
 #include <stdlib.h>
 #include <string.h>
@@ -73,10 +74,6 @@ static void lists_to_csr(EList *ls, int n, int with_w, int **off, int **tgt, dou
 }
 
 /* ───────────────────────── node2vec_train ───────────────────────── */
-
-/* mn_vtab_hnsw.c: the output step straight into a live hnsw_index (1 done, 0 not applicable, -1 error) */
-int mn_vtab_hnsw_fill_from_n2v(sqlite3 *db, const char *table, int n, const int *off, const int *adj, const mn_n2v_params *prm,
-                               int *inserted, char **err);
 
 static void fn_node2vec_train(sqlite3_context *ctx, int argc, sqlite3_value **argv) {
     if (argc < 13) {

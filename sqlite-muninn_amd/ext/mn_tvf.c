@@ -1,7 +1,8 @@
 /*
  * mn_tvf.c — the one sqlite3_module behind graph_components, graph_pagerank, graph_node_betweenness, graph_edge_betweenness,
- * graph_closeness, graph_degree, graph_leiden, graph_bfs, graph_dfs, graph_shortest_path and graph_select (mn_tvf.h).  The descriptor
- * travels as the module's pAux; the entry points below read it and never ask which function they serve.
+ * graph_closeness, graph_degree, graph_leiden, graph_bfs, graph_dfs, graph_shortest_path, graph_select, hnsw_search_batch,
+ * hnsw_search_exact and hnsw_knn_graph (mn_tvf.h).  The descriptor travels as the module's pAux; the entry points below read it
+ * and never ask which function they serve.  At the end, the statement helpers the table modules share.
  */
 #include "mn_tvf.h"
 
@@ -83,6 +84,7 @@ static void tvf_clear(MnTvfCursor *c) {
     c->n = c->pos = 0;
     c->eof = 1;
     c->oom = 0;
+    c->k = 0;
     c->q = 0.0;
     c->label = 0;
 }
@@ -127,7 +129,9 @@ static int tvf_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
 }
 
 static int tvf_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
-    *out = ((MnTvfCursor *)cur)->pos;
+    MnTvfCursor *c = (MnTvfCursor *)cur;
+    const MnTvf *def = mn_tvf_vtab(c)->def;
+    *out = def->rowid ? def->rowid(c) : c->pos;
     return SQLITE_OK;
 }
 
@@ -191,4 +195,21 @@ int mn_sql_compiles_owned(sqlite3 *db, char *sql) {
     sqlite3_free(sql);
     sqlite3_finalize(st);
     return rc == SQLITE_OK;
+}
+
+int mn_sql_exec_owned(sqlite3 *db, char *sql) {
+    if (!sql)
+        return SQLITE_NOMEM;
+    int rc = sqlite3_exec(db, sql, 0, 0, 0);
+    sqlite3_free(sql);
+    return rc;
+}
+
+int mn_sql_prepare_owned(sqlite3 *db, char *sql, sqlite3_stmt **st) {
+    *st = 0;
+    if (!sql)
+        return SQLITE_NOMEM;
+    int rc = sqlite3_prepare_v2(db, sql, -1, st, 0);
+    sqlite3_free(sql);
+    return rc;
 }

@@ -1,5 +1,5 @@
 /*
- * mn_tvf.h — the scaffold of the eponymous graph table-valued functions (mn_tvf.c): one vtab, one cursor, one sqlite3_module.
+ * mn_tvf.h — the scaffold of the eponymous table-valued functions, graph_* and hnsw_* (mn_tvf.c): one vtab, one cursor, one sqlite3_module.
  * A function is a descriptor (MnTvf) plus its xFilter and xColumn bodies; everything else — connect, the three xBestIndex
  * rules the reference uses, open / close / next / eof / rowid, freeing what a statement owned — is here once.
  * Exported names carry mn_: the integrated build (oracle/Makefile) links these files next to the reference's own.
@@ -20,7 +20,7 @@ enum {
                                    (graph_best_index_common, src/graph_common.h:62-96); decoded by mn_tvf_args */
 };
 
-#define MN_TVF_SLOTS 4
+#define MN_TVF_SLOTS 5
 #define MN_TVF_MAX_HIDDEN 10
 
 typedef struct MnTvf MnTvf;
@@ -37,8 +37,9 @@ typedef struct {
     int n_ids;
     void *buf[MN_TVF_SLOTS]; /* result arrays (owned; mn_tvf_alloc) */
     char *lone;              /* the text of an answer that is one row naming one node (owned; mn_tvf_lone_row) */
-    long long n, pos;        /* rows, and the current one: rowid = pos */
+    long long n, pos;        /* rows, and the current one: rowid = pos unless the descriptor has a rowid of its own */
     int eof, oom;
+    int k;             /* hnsw_*: the width of a group of the [groups][k] answer */
     double q;          /* graph_leiden: the partition's modularity */
     const char *label; /* graph_select: the direction column, a static string */
 } MnTvfCursor;
@@ -51,6 +52,7 @@ struct MnTvf {
     double cost;                /* the plan's cost with them */
     int (*filter)(MnTvfCursor *c, int idxNum, int argc, sqlite3_value **argv); /* on a cleared cursor */
     void (*column)(const MnTvfCursor *c, sqlite3_context *ctx, int col);
+    long long (*rowid)(const MnTvfCursor *c); /* optional: NULL means pos */
 };
 
 int mn_tvf_register(sqlite3 *db, const MnTvf *def);
@@ -78,6 +80,11 @@ int mn_env_graph_mode(void);
 /* whether the statement mn_sql_compiles(db, "format", ...) spells with sqlite3_mprintf's formats compiles */
 int mn_sql_compiles_owned(sqlite3 *db, char *sql);
 #define mn_sql_compiles(db, ...) mn_sql_compiles_owned(db, sqlite3_mprintf(__VA_ARGS__))
+
+/* Run, or compile into *st, a statement spelt with sqlite3_mprintf: the text is freed here, and a text that could not be
+ * allocated is SQLITE_NOMEM.  *st is NULL unless the result is SQLITE_OK. */
+int mn_sql_exec_owned(sqlite3 *db, char *sql);
+int mn_sql_prepare_owned(sqlite3 *db, char *sql, sqlite3_stmt **st);
 
 /* mn_graph_sql.c: an edge table (or a graph_adjacency table) → device graph + node ids */
 int mn_sql_load_graph(sqlite3 *db, const char *who, const char *edge_table, const char *src_col, const char *dst_col,

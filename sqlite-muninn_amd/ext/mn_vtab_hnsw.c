@@ -23,11 +23,10 @@
  *   fast     as deferred, but the queue is built with the batch-synchronous schedule (DESIGN.md §4:
  *            a different, equally good graph; orders of magnitude faster for bulk loads).
  */
-#include "../../include/muninn_hip.h"
-#include "mn_sqlite_abi.h"
+#include "mn_vtab_hnsw.h"
 #include "mn_nodemap.h"
+#include "mn_tvf.h" /* mn_sql_exec_owned, mn_sql_prepare_owned */
 
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -182,26 +181,18 @@ static int parse_args(int argc, const char *const *argv, Params *p, char **err) 
     return SQLITE_OK;
 }
 
-static int run_sql(sqlite3 *db, char *sql) {
-    if (!sql)
-        return SQLITE_NOMEM;
-    int rc = sqlite3_exec(db, sql, 0, 0, 0);
-    sqlite3_free(sql);
-    return rc;
-}
-
 /* src/hnsw_vtab.c:138-181 — byte-compatible shadow schema */
 static int make_shadow_tables(sqlite3 *db, const char *t) {
-    int rc = run_sql(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_config\" (key TEXT PRIMARY KEY, value TEXT NOT NULL)", t));
+    int rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_config\" (key TEXT PRIMARY KEY, value TEXT NOT NULL)", t));
     if (rc == SQLITE_OK)
-        rc = run_sql(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_nodes\" (  id INTEGER PRIMARY KEY,  vector BLOB NOT NULL,"
-                                         "  level INTEGER NOT NULL,  deleted INTEGER NOT NULL DEFAULT 0)", t));
+        rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_nodes\" (  id INTEGER PRIMARY KEY,  vector BLOB NOT NULL,"
+                                                   "  level INTEGER NOT NULL,  deleted INTEGER NOT NULL DEFAULT 0)", t));
     if (rc == SQLITE_OK)
-        rc = run_sql(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_edges\" (  source_id INTEGER NOT NULL,"
-                                         "  target_id INTEGER NOT NULL,  level INTEGER NOT NULL,  distance REAL NOT NULL,"
-                                         "  PRIMARY KEY (source_id, level, target_id)) WITHOUT ROWID", t));
+        rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE TABLE IF NOT EXISTS \"%w_edges\" (  source_id INTEGER NOT NULL,"
+                                                   "  target_id INTEGER NOT NULL,  level INTEGER NOT NULL,  distance REAL NOT NULL,"
+                                                   "  PRIMARY KEY (source_id, level, target_id)) WITHOUT ROWID", t));
     if (rc == SQLITE_OK)
-        rc = run_sql(db, sqlite3_mprintf("CREATE INDEX IF NOT EXISTS \"%w_edges_rev\" ON \"%w_edges\"(target_id, level)", t, t));
+        rc = mn_sql_exec_owned(db, sqlite3_mprintf("CREATE INDEX IF NOT EXISTS \"%w_edges_rev\" ON \"%w_edges\"(target_id, level)", t, t));
     return rc;
 }
 
@@ -217,11 +208,11 @@ static int write_config(VtabHnsw *v) {
         sqlite3_reset(v->st_cfg);
         return rc;
     }
-    return run_sql(v->db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\" (key, value) VALUES ('dimensions', '%d'),"
-                                          " ('metric', '%d'), ('m', '%d'), ('ef_construction', '%d'),"
-                                          " ('entry_point', '%lld'), ('max_level', '%d')",
-                                          v->name, v->dim, v->metric, v->m, v->efc,
-                                          (long long)mn_hnsw_entry_point(v->index), mn_hnsw_max_level(v->index)));
+    return mn_sql_exec_owned(v->db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\" (key, value) VALUES ('dimensions', '%d'),"
+                                                    " ('metric', '%d'), ('m', '%d'), ('ef_construction', '%d'),"
+                                                    " ('entry_point', '%lld'), ('max_level', '%d')",
+                                                    v->name, v->dim, v->metric, v->m, v->efc,
+                                                    (long long)mn_hnsw_entry_point(v->index), mn_hnsw_max_level(v->index)));
 }
 
 /* src/hnsw_vtab.c:201-234 */
@@ -232,10 +223,8 @@ static int read_config(sqlite3 *db, const char *t, Params *p, sqlite3_int64 *ent
     p->efc = 200;
     *entry = -1;
     *max_level = -1;
-    char *sql = sqlite3_mprintf("SELECT key, value FROM \"%w_config\"", t);
     sqlite3_stmt *st = 0;
-    int rc = sqlite3_prepare_v2(db, sql, -1, &st, 0);
-    sqlite3_free(sql);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT key, value FROM \"%w_config\"", t), &st);
     if (rc != SQLITE_OK)
         return rc;
     while (sqlite3_step(st) == SQLITE_ROW) {
@@ -357,90 +346,107 @@ static int pend_add(VtabHnsw *v, sqlite3_int64 id, const float *vec) {
     return SQLITE_OK;
 }
 
-/* Shadow rows for everything the device marked since the last call: persist_node (src/hnsw_vtab.c:237-283)
- * for every new node and every node that was a neighbour of a new node when it was linked (:755-768),
- * once per node instead of once per insert that touched it.  new_ids/new_vecs = the queue just applied. */
-static int persist_marked(VtabHnsw *v, const sqlite3_int64 *new_ids, const float *new_vecs, int n_new) {
-    sqlite3_stmt *st = 0;
-    char *sql = sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_nodes\" (id, vector, level, deleted) VALUES (?, ?, ?, 0)", v->name);
-    int rc = sqlite3_prepare_v2(v->db, sql, -1, &st, 0);
-    sqlite3_free(sql);
-    if (rc != SQLITE_OK)
-        return rc;
-    for (int i = 0; i < n_new && rc == SQLITE_OK; i++) {
-        sqlite3_bind_int64(st, 1, new_ids[i]);
-        sqlite3_bind_blob(st, 2, new_vecs + (size_t)i * v->dim, v->dim * (int)sizeof(float), SQLITE_STATIC);
-        sqlite3_bind_int(st, 3, mn_hnsw_node_level(v->index, new_ids[i]));
-        rc = sqlite3_step(st) == SQLITE_DONE ? SQLITE_OK : SQLITE_ERROR;
-        sqlite3_reset(st);
-    }
-    sqlite3_finalize(st);
-    if (rc != SQLITE_OK)
-        return rc;
+/* ── shadow rows ── */
+#define NODE_UPSERT "INSERT OR REPLACE INTO \"%w_nodes\" (id, vector, level, deleted) VALUES (?, ?, ?, 0)"
 
-    int64_t cap = (int64_t)n_new * (1 + v->m) + 1024, nd;
-    int64_t *marked = 0;
+/* one row of "{t}_nodes" through a statement compiled from NODE_UPSERT */
+static int put_node(VtabHnsw *v, sqlite3_stmt *st, sqlite3_int64 id, const float *vec) {
+    sqlite3_bind_int64(st, 1, id);
+    sqlite3_bind_blob(st, 2, vec, v->dim * (int)sizeof(float), SQLITE_STATIC);
+    sqlite3_bind_int(st, 3, mn_hnsw_node_level(v->index, id));
+    int rc = sqlite3_step(st) == SQLITE_DONE ? SQLITE_OK : SQLITE_ERROR;
+    sqlite3_reset(st);
+    return rc;
+}
+
+/* the four columns of "{t}_edges" as mn_hnsw_edges_of fills them */
+typedef struct {
+    int64_t *src, *dst;
+    int *lvl;
+    float *dist;
+    int64_t cap;
+} EdgeBuf;
+
+static void edges_free(EdgeBuf *e) {
+    free(e->src);
+    free(e->dst);
+    free(e->lvl);
+    free(e->dist);
+    memset(e, 0, sizeof(*e));
+}
+static void edges_alloc(EdgeBuf *e, int64_t cap) { /* whatever it held is gone; out of memory: it holds nothing, cap 0 */
+    edges_free(e);
+    e->src = (int64_t *)malloc((size_t)cap * sizeof(int64_t));
+    e->dst = (int64_t *)malloc((size_t)cap * sizeof(int64_t));
+    e->lvl = (int *)malloc((size_t)cap * sizeof(int));
+    e->dist = (float *)malloc((size_t)cap * sizeof(float));
+    e->cap = cap;
+    if (!e->src || !e->dst || !e->lvl || !e->dist)
+        edges_free(e);
+}
+
+static int persist_error(VtabHnsw *v, const char *what) {
+    sqlite3_free(v->base.zErrMsg);
+    v->base.zErrMsg = sqlite3_mprintf("hnsw_index: %s (%s)", what, mn_last_error());
+    return SQLITE_ERROR;
+}
+
+/* persist_marked, step 1: the node rows of the queue just applied */
+static int persist_new_nodes(VtabHnsw *v, const sqlite3_int64 *new_ids, const float *new_vecs, int n_new) {
+    sqlite3_stmt *st = 0;
+    int rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf(NODE_UPSERT, v->name), &st);
+    for (int i = 0; i < n_new && rc == SQLITE_OK; i++)
+        rc = put_node(v, st, new_ids[i], new_vecs + (size_t)i * v->dim);
+    sqlite3_finalize(st);
+    return rc;
+}
+
+/* step 2: everything the device marked since the last call; *marked is the caller's to free */
+static int take_persist_set(VtabHnsw *v, int n_new, int64_t **marked, int64_t *nd) {
+    int64_t cap = (int64_t)n_new * (1 + v->m) + 1024;
     for (;;) {
-        marked = (int64_t *)malloc((size_t)cap * sizeof(int64_t));
-        if (!marked)
+        *marked = (int64_t *)malloc((size_t)cap * sizeof(int64_t));
+        if (!*marked)
             return SQLITE_NOMEM;
-        nd = mn_hnsw_take_dirty(v->index, marked, cap);
-        if (nd <= cap)
+        *nd = mn_hnsw_take_dirty(v->index, *marked, cap);
+        if (*nd <= cap)
             break;
-        free(marked);
-        cap = nd;
+        free(*marked);
+        cap = *nd;
     }
-    if (nd < 0) {
-        free(marked);
-        sqlite3_free(v->base.zErrMsg);
-        v->base.zErrMsg = sqlite3_mprintf("hnsw_index: cannot read the persist set (%s)", mn_last_error());
-        return SQLITE_ERROR;
+    return *nd < 0 ? persist_error(v, "cannot read the persist set") : SQLITE_OK;
+}
+
+/* step 3: persist_node upserts the node row of every neighbour as well (src/hnsw_vtab.c:243-256).  For a row that exists
+ * that changes nothing; it matters after a ROLLBACK, which takes shadow rows away while the index (the reference's
+ * in-memory one, ours in HBM) keeps the nodes: the next insert that links to such a node brings its row back.
+ * The result of put_node is not looked at here, and never was: a row that cannot be brought back does not fail the flush. */
+static int restore_neighbour_rows(VtabHnsw *v, const int64_t *marked, int64_t nd) {
+    sqlite3_stmt *has = 0, *put = 0;
+    int rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("SELECT 1 FROM \"%w_nodes\" WHERE id = ?", v->name), &has);
+    if (rc == SQLITE_OK)
+        rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf(NODE_UPSERT, v->name), &put);
+    float *vb = rc == SQLITE_OK ? (float *)malloc((size_t)v->dim * sizeof(float)) : 0;
+    for (int64_t i = 0; i < nd && vb; i++) {
+        if (pset_has(v, marked[i]))
+            continue;
+        sqlite3_bind_int64(has, 1, marked[i]);
+        const int present = sqlite3_step(has) == SQLITE_ROW;
+        sqlite3_reset(has);
+        if (!present && mn_hnsw_get_vector(v->index, marked[i], vb) == 0)
+            put_node(v, put, marked[i], vb);
     }
-    /* persist_node upserts the node row of every neighbour as well (src/hnsw_vtab.c:243-256).  For a row that exists
-     * that changes nothing; it matters after a ROLLBACK, which takes shadow rows away while the index (the reference's
-     * in-memory one, ours in HBM) keeps the nodes: the next insert that links to such a node brings its row back. */
-    {
-        sqlite3_stmt *has = 0, *put = 0;
-        sql = sqlite3_mprintf("SELECT 1 FROM \"%w_nodes\" WHERE id = ?", v->name);
-        rc = sqlite3_prepare_v2(v->db, sql, -1, &has, 0);
-        sqlite3_free(sql);
-        if (rc == SQLITE_OK) {
-            sql = sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_nodes\" (id, vector, level, deleted) VALUES (?, ?, ?, 0)", v->name);
-            rc = sqlite3_prepare_v2(v->db, sql, -1, &put, 0);
-            sqlite3_free(sql);
-        }
-        float *vb = rc == SQLITE_OK ? (float *)malloc((size_t)v->dim * sizeof(float)) : 0;
-        for (int64_t i = 0; i < nd && rc == SQLITE_OK && vb; i++) {
-            if (pset_has(v, marked[i]))
-                continue;
-            sqlite3_bind_int64(has, 1, marked[i]);
-            const int present = sqlite3_step(has) == SQLITE_ROW;
-            sqlite3_reset(has);
-            if (present || mn_hnsw_get_vector(v->index, marked[i], vb) != 0)
-                continue;
-            sqlite3_bind_int64(put, 1, marked[i]);
-            sqlite3_bind_blob(put, 2, vb, v->dim * (int)sizeof(float), SQLITE_STATIC);
-            sqlite3_bind_int(put, 3, mn_hnsw_node_level(v->index, marked[i]));
-            sqlite3_step(put);
-            sqlite3_reset(put);
-        }
-        free(vb);
-        sqlite3_finalize(has);
-        sqlite3_finalize(put);
-        if (rc != SQLITE_OK) {
-            free(marked);
-            return rc;
-        }
-    }
-    /* old edges of the pre-existing marked nodes (new nodes have none yet) */
-    sql = sqlite3_mprintf("DELETE FROM \"%w_edges\" WHERE source_id = ?", v->name);
-    rc = sqlite3_prepare_v2(v->db, sql, -1, &st, 0);
-    sqlite3_free(sql);
-    if (rc != SQLITE_OK) {
-        free(marked);
-        return rc;
-    }
-    for (int64_t i = 0; i < nd; i++) {
+    free(vb);
+    sqlite3_finalize(has);
+    sqlite3_finalize(put);
+    return rc;
+}
+
+/* step 4: old edges of the pre-existing marked nodes (new nodes have none yet) */
+static int delete_old_edges(VtabHnsw *v, const int64_t *marked, int64_t nd) {
+    sqlite3_stmt *st = 0;
+    int rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("DELETE FROM \"%w_edges\" WHERE source_id = ?", v->name), &st);
+    for (int64_t i = 0; i < nd && rc == SQLITE_OK; i++) {
         if (pset_has(v, marked[i]))
             continue;
         sqlite3_bind_int64(st, 1, marked[i]);
@@ -448,54 +454,61 @@ static int persist_marked(VtabHnsw *v, const sqlite3_int64 *new_ids, const float
         sqlite3_reset(st);
     }
     sqlite3_finalize(st);
+    return rc;
+}
 
-    sql = sqlite3_mprintf("INSERT INTO \"%w_edges\" (source_id, target_id, level, distance) VALUES (?, ?, ?, ?)", v->name);
-    rc = sqlite3_prepare_v2(v->db, sql, -1, &st, 0);
-    sqlite3_free(sql);
-    if (rc != SQLITE_OK) {
-        free(marked);
-        return rc;
-    }
-    const int CHUNK = 8192; /* nodes per device round trip */
-    int64_t ecap = (int64_t)CHUNK * 3 * v->m + 64;
-    int64_t *src = (int64_t *)malloc((size_t)ecap * sizeof(int64_t));
-    int64_t *dst = (int64_t *)malloc((size_t)ecap * sizeof(int64_t));
-    int *lvl = (int *)malloc((size_t)ecap * sizeof(int));
-    float *dist = (float *)malloc((size_t)ecap * sizeof(float));
+/* step 5: the lists of every marked node as they stand, read from the device CHUNK nodes per round trip */
+static int insert_edges(VtabHnsw *v, const int64_t *marked, int64_t nd) {
+    const int CHUNK = 8192;
+    sqlite3_stmt *st = 0;
+    int rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("INSERT INTO \"%w_edges\" (source_id, target_id, level, distance) VALUES (?, ?, ?, ?)",
+                                                         v->name), &st);
+    EdgeBuf e = {0};
+    if (rc == SQLITE_OK)
+        edges_alloc(&e, (int64_t)CHUNK * 3 * v->m + 64);
     for (int64_t pos = 0; pos < nd && rc == SQLITE_OK; pos += CHUNK) {
-        int n = (int)(nd - pos < CHUNK ? nd - pos : CHUNK);
-        int64_t ne = -1;
-        if (src && dst && lvl && dist)
-            ne = mn_hnsw_edges_of(v->index, marked + pos, n, src, dst, lvl, dist, ecap);
-        if (ne > ecap) { /* more edges than the guess: grow and ask again */
-            free(src); free(dst); free(lvl); free(dist);
-            ecap = ne;
-            src = (int64_t *)malloc((size_t)ecap * sizeof(int64_t));
-            dst = (int64_t *)malloc((size_t)ecap * sizeof(int64_t));
-            lvl = (int *)malloc((size_t)ecap * sizeof(int));
-            dist = (float *)malloc((size_t)ecap * sizeof(float));
+        const int n = (int)(nd - pos < CHUNK ? nd - pos : CHUNK);
+        const int64_t ne = e.cap ? mn_hnsw_edges_of(v->index, marked + pos, n, e.src, e.dst, e.lvl, e.dist, e.cap) : -1;
+        if (ne > e.cap) { /* more edges than the guess: grow and ask again */
+            edges_alloc(&e, ne);
             pos -= CHUNK;
             continue;
         }
         if (ne < 0) {
-            sqlite3_free(v->base.zErrMsg);
-            v->base.zErrMsg = sqlite3_mprintf("hnsw_index: cannot read neighbour lists (%s)", mn_last_error());
-            rc = SQLITE_ERROR;
+            rc = persist_error(v, "cannot read neighbour lists");
             break;
         }
-        for (int64_t e = 0; e < ne; e++) {
-            sqlite3_bind_int64(st, 1, src[e]);
-            sqlite3_bind_int64(st, 2, dst[e]);
-            sqlite3_bind_int(st, 3, lvl[e]);
-            sqlite3_bind_double(st, 4, (double)dist[e]);
+        for (int64_t i = 0; i < ne; i++) {
+            sqlite3_bind_int64(st, 1, e.src[i]);
+            sqlite3_bind_int64(st, 2, e.dst[i]);
+            sqlite3_bind_int(st, 3, e.lvl[i]);
+            sqlite3_bind_double(st, 4, (double)e.dist[i]);
             sqlite3_step(st);
             sqlite3_reset(st);
         }
     }
     sqlite3_finalize(st);
-    free(src); free(dst); free(lvl); free(dist); free(marked);
+    edges_free(&e);
+    return rc;
+}
+
+/* Shadow rows for everything the device marked since the last call: persist_node (src/hnsw_vtab.c:237-283)
+ * for every new node and every node that was a neighbour of a new node when it was linked (:755-768),
+ * once per node instead of once per insert that touched it.  new_ids/new_vecs = the queue just applied. */
+static int persist_marked(VtabHnsw *v, const sqlite3_int64 *new_ids, const float *new_vecs, int n_new) {
+    int64_t *marked = 0, nd = 0;
+    int rc = persist_new_nodes(v, new_ids, new_vecs, n_new);
     if (rc == SQLITE_OK)
-        rc = write_config(v);
+        rc = take_persist_set(v, n_new, &marked, &nd);
+    if (rc == SQLITE_OK)
+        rc = restore_neighbour_rows(v, marked, nd);
+    if (rc == SQLITE_OK)
+        rc = delete_old_edges(v, marked, nd);
+    if (rc == SQLITE_OK)
+        rc = insert_edges(v, marked, nd);
+    if (rc == SQLITE_OK)
+        rc = write_config(v); /* step 6 */
+    free(marked);
     return rc;
 }
 
@@ -527,25 +540,19 @@ static int delta_prepare(VtabHnsw *v) {
     v->chlog = (mn_edge_change *)malloc((size_t)MN_DELTA_CAP * sizeof(mn_edge_change));
     if (!v->chlog)
         return SQLITE_NOMEM;
-    static const char *const Q[4] = {
-        "INSERT OR REPLACE INTO \"%w_nodes\" (id, vector, level, deleted) VALUES (?, ?, ?, 0)",
+    static const char *const Q[3] = {
+        NODE_UPSERT,
         "INSERT OR REPLACE INTO \"%w_edges\" (source_id, target_id, level, distance) VALUES (?, ?, ?, ?)",
-        "DELETE FROM \"%w_edges\" WHERE source_id = ? AND level = ? AND target_id = ?",
-        0};
+        "DELETE FROM \"%w_edges\" WHERE source_id = ? AND level = ? AND target_id = ?"};
     sqlite3_stmt **dst[3] = {&v->st_node, &v->st_edge_put, &v->st_edge_del};
     int rc = SQLITE_OK;
-    for (int i = 0; i < 3 && rc == SQLITE_OK; i++) {
-        char *sql = sqlite3_mprintf(Q[i], v->name);
-        rc = sql ? sqlite3_prepare_v2(v->db, sql, -1, dst[i], 0) : SQLITE_NOMEM;
-        sqlite3_free(sql);
-    }
-    if (rc == SQLITE_OK) {
-        char *sql = sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\" (key, value) VALUES ('dimensions', '%d'),"
-                                    " ('metric', '%d'), ('m', '%d'), ('ef_construction', '%d'), ('entry_point', ?1), ('max_level', ?2)",
-                                    v->name, v->dim, v->metric, v->m, v->efc);
-        rc = sql ? sqlite3_prepare_v2(v->db, sql, -1, &v->st_cfg, 0) : SQLITE_NOMEM;
-        sqlite3_free(sql);
-    }
+    for (int i = 0; i < 3 && rc == SQLITE_OK; i++)
+        rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf(Q[i], v->name), dst[i]);
+    if (rc == SQLITE_OK)
+        rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("INSERT OR REPLACE INTO \"%w_config\" (key, value) VALUES ('dimensions', '%d'),"
+                                                         " ('metric', '%d'), ('m', '%d'), ('ef_construction', '%d'),"
+                                                         " ('entry_point', ?1), ('max_level', ?2)",
+                                                         v->name, v->dim, v->metric, v->m, v->efc), &v->st_cfg);
     if (rc != SQLITE_OK)
         delta_release(v);
     return rc;
@@ -567,11 +574,7 @@ static int insert_one_delta(VtabHnsw *v, sqlite3_int64 id, const float *vec, int
     if (*dev_rc != 0 || n_log < 0)
         return SQLITE_OK;
     *logged = 1;
-    sqlite3_bind_int64(v->st_node, 1, id);
-    sqlite3_bind_blob(v->st_node, 2, vec, v->dim * (int)sizeof(float), SQLITE_STATIC);
-    sqlite3_bind_int(v->st_node, 3, mn_hnsw_node_level(v->index, id));
-    rc = sqlite3_step(v->st_node) == SQLITE_DONE ? SQLITE_OK : SQLITE_ERROR;
-    sqlite3_reset(v->st_node);
+    rc = put_node(v, v->st_node, id, vec);
     for (int i = 0; i < n_log && rc == SQLITE_OK; i++) {
         const mn_edge_change *e = &v->chlog[i];
         sqlite3_stmt *st = e->op == 1 ? v->st_edge_put : v->st_edge_del;
@@ -636,9 +639,7 @@ static int flush_pending(VtabHnsw *v) {
 /* load_index_from_shadow (src/hnsw_vtab.c:286-341): nodes in rowid order, edges in primary-key order */
 static int load_from_shadow(VtabHnsw *v) {
     sqlite3_stmt *st = 0;
-    char *sql = sqlite3_mprintf("SELECT id, vector, level, deleted FROM \"%w_nodes\"", v->name);
-    int rc = sqlite3_prepare_v2(v->db, sql, -1, &st, 0);
-    sqlite3_free(sql);
+    int rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("SELECT id, vector, level, deleted FROM \"%w_nodes\"", v->name), &st);
     if (rc != SQLITE_OK)
         return rc;
     while (sqlite3_step(st) == SQLITE_ROW) {
@@ -651,9 +652,7 @@ static int load_from_shadow(VtabHnsw *v) {
         }
     }
     sqlite3_finalize(st);
-    sql = sqlite3_mprintf("SELECT source_id, target_id, level FROM \"%w_edges\"", v->name);
-    rc = sqlite3_prepare_v2(v->db, sql, -1, &st, 0);
-    sqlite3_free(sql);
+    rc = mn_sql_prepare_owned(v->db, sqlite3_mprintf("SELECT source_id, target_id, level FROM \"%w_edges\"", v->name), &st);
     if (rc != SQLITE_OK)
         return rc;
     while (sqlite3_step(st) == SQLITE_ROW) {
@@ -673,10 +672,20 @@ static int load_from_shadow(VtabHnsw *v) {
     return SQLITE_OK;
 }
 
-static VtabHnsw *new_vtab(sqlite3 *db, const char *name, const Params *p, mn_index *ix) {
+/* xCreate and xConnect: an empty index on the configured device, or the error worded; the table around it, entered in the live list */
+static int open_table(sqlite3 *db, const char *name, const Params *p, VtabHnsw **out, char **err) {
+    mn_index *ix = mn_hnsw_create_on(p->dimensions, p->metric, p->m, p->efc, mn_env_device());
+    if (!ix) {
+        /* (the reference reports SQLITE_NOMEM here, src/hnsw_vtab.c:380-383: its only cause is malloc; here the usual cause
+         * is the device — a wrong MUNINN_DEVICE, no GPU — and SQLITE_NOMEM would drop the message) */
+        *err = sqlite3_mprintf("hnsw_index: failed to allocate index (%s)%s", mn_last_error(), mn_env_device_hint());
+        return SQLITE_ERROR;
+    }
     VtabHnsw *v = (VtabHnsw *)sqlite3_malloc((int)sizeof(VtabHnsw));
-    if (!v)
-        return 0;
+    if (!v) {
+        mn_hnsw_destroy(ix);
+        return SQLITE_NOMEM;
+    }
     memset(v, 0, sizeof(*v));
     v->db = db;
     v->name = sqlite3_mprintf("%s", name);
@@ -690,12 +699,23 @@ static VtabHnsw *new_vtab(sqlite3 *db, const char *name, const Params *p, mn_ind
     const char *delta = getenv("MUNINN_HNSW_DELTA"); /* =0: whole-node rewrites always, as the reference does them */
     v->delta_ok = !(delta && !strcmp(delta, "0"));
     live_add(v);
-    return v;
+    *out = v;
+    return SQLITE_OK;
+}
+
+static void close_table(VtabHnsw *v) {
+    live_remove(v);
+    pend_free(v);
+    delta_release(v);
+    mn_hnsw_destroy(v->index);
+    sqlite3_free(v->name);
+    sqlite3_free(v);
 }
 
 static int x_create(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
     (void)aux;
     Params p;
+    VtabHnsw *v = 0;
     int rc = parse_args(argc, argv, &p, err);
     if (rc != SQLITE_OK)
         return rc;
@@ -707,18 +727,9 @@ static int x_create(sqlite3 *db, void *aux, int argc, const char *const *argv, s
         *err = sqlite3_mprintf("hnsw_index: failed to create shadow tables");
         return rc;
     }
-    mn_index *ix = mn_hnsw_create_on(p.dimensions, p.metric, p.m, p.efc, mn_env_device());
-    if (!ix) {
-        /* (the reference reports SQLITE_NOMEM here, src/hnsw_vtab.c:380-383: its only cause is malloc; here the usual cause
-         * is the device — a wrong MUNINN_DEVICE, no GPU — and SQLITE_NOMEM would drop the message) */
-        *err = sqlite3_mprintf("hnsw_index: failed to allocate index (%s)%s", mn_last_error(), mn_env_device_hint());
-        return SQLITE_ERROR;
-    }
-    VtabHnsw *v = new_vtab(db, argv[2], &p, ix);
-    if (!v) {
-        mn_hnsw_destroy(ix);
-        return SQLITE_NOMEM;
-    }
+    rc = open_table(db, argv[2], &p, &v, err);
+    if (rc != SQLITE_OK)
+        return rc;
     write_config(v);
     *out = &v->base;
     return SQLITE_OK;
@@ -728,6 +739,7 @@ static int x_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, 
     (void)aux;
     (void)argc;
     Params p;
+    VtabHnsw *v = 0;
     sqlite3_int64 entry;
     int max_level;
     int rc = read_config(db, argv[2], &p, &entry, &max_level);
@@ -740,54 +752,35 @@ static int x_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, 
         return SQLITE_ERROR;
     }
     rc = sqlite3_declare_vtab(db, SCHEMA);
+    if (rc == SQLITE_OK)
+        rc = open_table(db, argv[2], &p, &v, err);
     if (rc != SQLITE_OK)
         return rc;
-    mn_index *ix = mn_hnsw_create_on(p.dimensions, p.metric, p.m, p.efc, mn_env_device());
-    if (!ix) {
-        /* (the reference reports SQLITE_NOMEM here, src/hnsw_vtab.c:380-383: its only cause is malloc; here the usual cause
-         * is the device — a wrong MUNINN_DEVICE, no GPU — and SQLITE_NOMEM would drop the message) */
-        *err = sqlite3_mprintf("hnsw_index: failed to allocate index (%s)%s", mn_last_error(), mn_env_device_hint());
-        return SQLITE_ERROR;
-    }
-    VtabHnsw *v = new_vtab(db, argv[2], &p, ix);
-    if (!v) {
-        mn_hnsw_destroy(ix);
-        return SQLITE_NOMEM;
-    }
     rc = load_from_shadow(v);
     if (rc != SQLITE_OK) {
-        live_remove(v);
-        mn_hnsw_destroy(ix);
-        sqlite3_free(v->name);
-        sqlite3_free(v);
+        close_table(v);
         *err = sqlite3_mprintf("hnsw_index: failed to load index from shadow tables");
         return rc;
     }
-    mn_hnsw_set_entry(ix, entry, max_level);
+    mn_hnsw_set_entry(v->index, entry, max_level);
     *out = &v->base;
     return SQLITE_OK;
 }
 
 static int x_disconnect(sqlite3_vtab *vt) {
-    VtabHnsw *v = (VtabHnsw *)vt;
     if (getenv("MUNINN_PROFILE") && g_prof_rows)
         fprintf(stderr, "[muninn] %lld rows flushed: device %.3f s, shadow tables %.3f s\n", g_prof_rows, g_prof_dev_s, g_prof_sql_s);
-    live_remove(v);
-    pend_free(v);
-    delta_release(v);
-    mn_hnsw_destroy(v->index);
-    sqlite3_free(v->name);
-    sqlite3_free(v);
+    close_table((VtabHnsw *)vt);
     return SQLITE_OK;
 }
 
 static int x_destroy(sqlite3_vtab *vt) { /* src/hnsw_vtab.c:471-494 */
     VtabHnsw *v = (VtabHnsw *)vt;
     delta_release(v);
-    run_sql(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_config\"", v->name));
-    run_sql(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_nodes\"", v->name));
-    run_sql(v->db, sqlite3_mprintf("DROP INDEX IF EXISTS \"%w_edges_rev\"", v->name));
-    run_sql(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_edges\"", v->name));
+    mn_sql_exec_owned(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_config\"", v->name));
+    mn_sql_exec_owned(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_nodes\"", v->name));
+    mn_sql_exec_owned(v->db, sqlite3_mprintf("DROP INDEX IF EXISTS \"%w_edges_rev\"", v->name));
+    mn_sql_exec_owned(v->db, sqlite3_mprintf("DROP TABLE IF EXISTS \"%w_edges\"", v->name));
     return x_disconnect(vt);
 }
 
@@ -942,7 +935,7 @@ static int x_update(sqlite3_vtab *vt, int argc, sqlite3_value **argv, sqlite3_in
             v->base.zErrMsg = sqlite3_mprintf("hnsw_index: delete failed (%s)", mn_last_error());
             return SQLITE_ERROR;
         }
-        run_sql(v->db, sqlite3_mprintf("UPDATE \"%w_nodes\" SET deleted = 1 WHERE id = %lld", v->name, (long long)id));
+        mn_sql_exec_owned(v->db, sqlite3_mprintf("UPDATE \"%w_nodes\" SET deleted = 1 WHERE id = %lld", v->name, (long long)id));
         write_config(v);
         return SQLITE_OK;
     }
@@ -1075,395 +1068,6 @@ static sqlite3_module hnsw_module = {
     .xRollbackTo = x_rollback_to,
 };
 
-/* ───────────────────────── hnsw_search_batch: many queries, one launch ─────────────────────────
- * The reference's SQL surface answers one query per xFilter (src/hnsw_vtab.c:586-606).  This ADDITIVE
- * eponymous table-valued function exposes the batched device search without touching hnsw_index:
- *   SELECT query_idx, id, distance FROM hnsw_search_batch
- *    WHERE tbl = 'vec' AND queries = :blob AND k = 10 [AND ef_search = 128];
- * `queries` is nq * dimensions little-endian f32; rows come out grouped by query_idx, ascending distance.
- *
- * hnsw_search_exact is the same function over the exact search (mn_hnsw_search_exact_batch: the true k nearest live rows, ties
- * by insertion order, distances with the bits of the table's own metric), with an optional list of rowids to search among in
- * place of ef_search:
- *   SELECT query_idx, id, distance FROM hnsw_search_exact
- *    WHERE tbl = 'vec' AND queries = :blob AND k = 10 [AND allow = :int64_blob];
- * `allow` is n little-endian int64 rowids; rowids the table does not hold are ignored, an empty blob answers nothing. */
-typedef struct {
-    sqlite3_vtab base;
-    sqlite3 *db;
-    int exact; /* hnsw_search_exact: the fourth hidden column is `allow` */
-} BatchVtab;
-typedef struct {
-    sqlite3_vtab_cursor base;
-    int64_t *ids;
-    float *dists;
-    int *counts;
-    int nq, k, qi, ri;
-} BatchCur;
-enum { BC_QIDX = 0, BC_ID, BC_DIST, BC_TBL, BC_QUERIES, BC_K, BC_EF };
-
-static int b_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    (void)argc; (void)argv; (void)err;
-    int rc = sqlite3_declare_vtab(db, aux ? "CREATE TABLE x(query_idx INTEGER, id INTEGER, distance REAL, tbl TEXT HIDDEN,"
-                                            " queries BLOB HIDDEN, k INTEGER HIDDEN, allow BLOB HIDDEN)"
-                                          : "CREATE TABLE x(query_idx INTEGER, id INTEGER, distance REAL, tbl TEXT HIDDEN,"
-                                            " queries BLOB HIDDEN, k INTEGER HIDDEN, ef_search INTEGER HIDDEN)");
-    if (rc != SQLITE_OK)
-        return rc;
-    BatchVtab *v = (BatchVtab *)sqlite3_malloc((int)sizeof(BatchVtab));
-    if (!v)
-        return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    v->exact = aux != 0;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-static int b_disconnect(sqlite3_vtab *v) {
-    sqlite3_free(v);
-    return SQLITE_OK;
-}
-static int b_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
-    (void)v;
-    int which[4] = {-1, -1, -1, -1};
-    for (int i = 0; i < ii->nConstraint; i++) {
-        if (!ii->aConstraint[i].usable || ii->aConstraint[i].op != SQLITE_INDEX_CONSTRAINT_EQ)
-            continue;
-        int col = ii->aConstraint[i].iColumn;
-        if (col >= BC_TBL && col <= BC_EF)
-            which[col - BC_TBL] = i;
-    }
-    int arg = 1, mask = 0;
-    for (int j = 0; j < 4; j++)
-        if (which[j] >= 0) {
-            ii->aConstraintUsage[which[j]].argvIndex = arg++;
-            ii->aConstraintUsage[which[j]].omit = 1;
-            mask |= 1 << j;
-        }
-    ii->idxNum = mask;
-    ii->estimatedCost = (mask & 0x7) == 0x7 ? 100.0 : 1e12;
-    return SQLITE_OK;
-}
-static int b_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
-    (void)v;
-    BatchCur *c = (BatchCur *)calloc(1, sizeof(BatchCur));
-    if (!c)
-        return SQLITE_NOMEM;
-    *out = &c->base;
-    return SQLITE_OK;
-}
-static void b_clear(BatchCur *c) {
-    free(c->ids);
-    free(c->dists);
-    free(c->counts);
-    c->ids = 0;
-    c->dists = 0;
-    c->counts = 0;
-    c->nq = 0;
-}
-static int b_close(sqlite3_vtab_cursor *cur) {
-    b_clear((BatchCur *)cur);
-    free(cur);
-    return SQLITE_OK;
-}
-static void b_skip_empty(BatchCur *c) {
-    while (c->qi < c->nq && c->ri >= c->counts[c->qi]) {
-        c->qi++;
-        c->ri = 0;
-    }
-}
-static int b_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
-    (void)idxStr;
-    BatchCur *c = (BatchCur *)cur;
-    BatchVtab *bv = (BatchVtab *)cur->pVtab;
-    b_clear(c);
-    c->qi = c->ri = 0;
-    if ((idxNum & 0x7) != 0x7 || argc < 3)
-        return SQLITE_OK;
-    const char *tbl = (const char *)sqlite3_value_text(argv[0]);
-    const float *q = (const float *)sqlite3_value_blob(argv[1]);
-    int qbytes = sqlite3_value_bytes(argv[1]);
-    int k = sqlite3_value_int(argv[2]);
-    int ef = (idxNum & 0x8) && argc >= 4 ? sqlite3_value_int(argv[3]) : 2 * k;
-    const char *fn = bv->exact ? "hnsw_search_exact" : "hnsw_search_batch";
-    VtabHnsw *v = tbl ? live_find(bv->db, tbl) : 0;
-    if (!v && tbl) { /* not connected yet on this connection: touching the table connects it */
-        char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", tbl);
-        sqlite3_exec(bv->db, sql, 0, 0, 0);
-        sqlite3_free(sql);
-        v = live_find(bv->db, tbl);
-    }
-    if (!v) {
-        bv->base.zErrMsg = sqlite3_mprintf("%s: no hnsw_index table named '%s'", fn, tbl ? tbl : "");
-        return SQLITE_ERROR;
-    }
-    if (flush_pending(v) != SQLITE_OK) {
-        bv->base.zErrMsg = sqlite3_mprintf("%s: %s", fn, v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
-        return SQLITE_ERROR;
-    }
-    int row = v->dim * (int)sizeof(float);
-    if (k <= 0 || qbytes <= 0 || qbytes % row != 0) {
-        bv->base.zErrMsg = sqlite3_mprintf("%s: queries must be a multiple of %d bytes (%d-dim f32), got %d", fn, row, v->dim, qbytes);
-        return SQLITE_ERROR;
-    }
-    const int has_allow = bv->exact && (idxNum & 0x8) && argc >= 4 && sqlite3_value_type(argv[3]) != SQLITE_NULL;
-    const int64_t *allow = has_allow ? (const int64_t *)sqlite3_value_blob(argv[3]) : 0;
-    const int abytes = has_allow ? sqlite3_value_bytes(argv[3]) : 0;
-    if (abytes % 8 != 0) {
-        bv->base.zErrMsg = sqlite3_mprintf("%s: allow must be a multiple of 8 bytes (int64 rowids), got %d", fn, abytes);
-        return SQLITE_ERROR;
-    }
-    c->nq = qbytes / row;
-    c->k = k;
-    c->ids = (int64_t *)malloc((size_t)c->nq * k * sizeof(int64_t));
-    c->dists = (float *)malloc((size_t)c->nq * k * sizeof(float));
-    c->counts = (int *)malloc((size_t)c->nq * sizeof(int));
-    if (!c->ids || !c->dists || !c->counts)
-        return SQLITE_NOMEM;
-    static const int64_t none = 0; /* an empty blob has no address: any non-NULL pointer says "filter, nothing allowed" */
-    if ((bv->exact ? mn_hnsw_search_exact_batch(v->index, q, c->nq, k, has_allow ? (abytes ? allow : &none) : 0, abytes / 8,
-                                                c->ids, c->dists, c->counts)
-                   : mn_hnsw_search_batch(v->index, q, c->nq, k, ef, c->ids, c->dists, c->counts)) != 0) {
-        bv->base.zErrMsg = sqlite3_mprintf("%s: %s", fn, mn_last_error());
-        return SQLITE_ERROR;
-    }
-    b_skip_empty(c);
-    return SQLITE_OK;
-}
-static int b_next(sqlite3_vtab_cursor *cur) {
-    BatchCur *c = (BatchCur *)cur;
-    c->ri++;
-    b_skip_empty(c);
-    return SQLITE_OK;
-}
-static int b_eof(sqlite3_vtab_cursor *cur) {
-    BatchCur *c = (BatchCur *)cur;
-    return c->qi >= c->nq;
-}
-static int b_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
-    BatchCur *c = (BatchCur *)cur;
-    size_t at = (size_t)c->qi * c->k + c->ri;
-    switch (col) {
-    case BC_QIDX: sqlite3_result_int(ctx, c->qi); break;
-    case BC_ID: sqlite3_result_int64(ctx, c->ids[at]); break;
-    case BC_DIST: sqlite3_result_double(ctx, (double)c->dists[at]); break;
-    default: sqlite3_result_null(ctx); break;
-    }
-    return SQLITE_OK;
-}
-static int b_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
-    BatchCur *c = (BatchCur *)cur;
-    *out = (sqlite3_int64)c->qi * c->k + c->ri;
-    return SQLITE_OK;
-}
-static sqlite3_module batch_module = {
-    .iVersion = 0,
-    .xCreate = 0,
-    .xConnect = b_connect,
-    .xBestIndex = b_best_index,
-    .xDisconnect = b_disconnect,
-    .xDestroy = b_disconnect,
-    .xOpen = b_open,
-    .xClose = b_close,
-    .xFilter = b_filter,
-    .xNext = b_next,
-    .xEof = b_eof,
-    .xColumn = b_column,
-    .xRowid = b_rowid,
-};
-
-/* ───────────────────────── hnsw_knn_graph: the exact k-NN graph of a table's own rows ─────────────────────────
- * The reference's entity-resolution pipeline (src/llama_er.c:207-286) reads every row of an hnsw_index back, asks the graph for
- * its k + 1 nearest rows and keeps the pairs under a distance threshold: one SELECT and one MATCH per row.  This ADDITIVE
- * eponymous table-valued function answers that loop in one statement, exactly, without a vector leaving the device
- * (mn_hnsw_knn_graph): for every live row its k nearest OTHER live rows, ties by insertion order, distances with the bits of the
- * table's own metric, only those with distance <= max_distance when one is given:
- *   SELECT src, dst, distance, rank FROM hnsw_knn_graph WHERE tbl = 'vec' AND k = 10 [AND max_distance = 0.3];
- * src and dst are rowids, rank is 0-based; rows come ordered by (src's insertion order, rank) — an edge list graph_leiden,
- * node2vec_train and graph_closeness take as it is. */
-typedef struct {
-    sqlite3_vtab base;
-    sqlite3 *db;
-} KnnVtab;
-typedef struct {
-    sqlite3_vtab_cursor base;
-    int64_t *src; /* [n] rowid of every slot */
-    int64_t *ids; /* [n][k] */
-    float *dists; /* [n][k] */
-    int *counts;  /* [n], -1: a deleted slot */
-    int n, k, si, ri;
-} KnnCur;
-enum { KC_SRC = 0, KC_DST, KC_DIST, KC_RANK, KC_TBL, KC_K, KC_MAXD };
-
-static int k_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    (void)aux; (void)argc; (void)argv; (void)err;
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(src INTEGER, dst INTEGER, distance REAL, rank INTEGER, tbl TEXT HIDDEN,"
-                                      " k INTEGER HIDDEN, max_distance REAL HIDDEN)");
-    if (rc != SQLITE_OK)
-        return rc;
-    KnnVtab *v = (KnnVtab *)sqlite3_malloc((int)sizeof(KnnVtab));
-    if (!v)
-        return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-static int k_disconnect(sqlite3_vtab *v) {
-    sqlite3_free(v);
-    return SQLITE_OK;
-}
-static int k_best_index(sqlite3_vtab *v, sqlite3_index_info *ii) {
-    (void)v;
-    int which[3] = {-1, -1, -1};
-    for (int i = 0; i < ii->nConstraint; i++) {
-        if (!ii->aConstraint[i].usable || ii->aConstraint[i].op != SQLITE_INDEX_CONSTRAINT_EQ)
-            continue;
-        int col = ii->aConstraint[i].iColumn;
-        if (col >= KC_TBL && col <= KC_MAXD)
-            which[col - KC_TBL] = i;
-    }
-    int arg = 1, mask = 0;
-    for (int j = 0; j < 3; j++)
-        if (which[j] >= 0) {
-            ii->aConstraintUsage[which[j]].argvIndex = arg++;
-            ii->aConstraintUsage[which[j]].omit = 1;
-            mask |= 1 << j;
-        }
-    ii->idxNum = mask;
-    ii->estimatedCost = (mask & 0x3) == 0x3 ? 100.0 : 1e12;
-    return SQLITE_OK;
-}
-static int k_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
-    (void)v;
-    KnnCur *c = (KnnCur *)calloc(1, sizeof(KnnCur));
-    if (!c)
-        return SQLITE_NOMEM;
-    *out = &c->base;
-    return SQLITE_OK;
-}
-static void k_clear(KnnCur *c) {
-    free(c->src);
-    free(c->ids);
-    free(c->dists);
-    free(c->counts);
-    c->src = 0;
-    c->ids = 0;
-    c->dists = 0;
-    c->counts = 0;
-    c->n = 0;
-}
-static int k_close(sqlite3_vtab_cursor *cur) {
-    k_clear((KnnCur *)cur);
-    free(cur);
-    return SQLITE_OK;
-}
-static void k_skip_empty(KnnCur *c) {
-    while (c->si < c->n && c->ri >= c->counts[c->si]) {
-        c->si++;
-        c->ri = 0;
-    }
-}
-static int k_filter(sqlite3_vtab_cursor *cur, int idxNum, const char *idxStr, int argc, sqlite3_value **argv) {
-    (void)idxStr;
-    KnnCur *c = (KnnCur *)cur;
-    KnnVtab *kv = (KnnVtab *)cur->pVtab;
-    k_clear(c);
-    c->si = c->ri = 0;
-    if ((idxNum & 0x3) != 0x3 || argc < 2)
-        return SQLITE_OK;
-    const char *tbl = (const char *)sqlite3_value_text(argv[0]);
-    const int k = sqlite3_value_int(argv[1]);
-    const int has_r = (idxNum & 0x4) && argc >= 3 && sqlite3_value_type(argv[2]) != SQLITE_NULL;
-    const float r = has_r ? (float)sqlite3_value_double(argv[2]) : INFINITY;
-    VtabHnsw *v = tbl ? live_find(kv->db, tbl) : 0;
-    if (!v && tbl) { /* not connected yet on this connection: touching the table connects it */
-        char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", tbl);
-        sqlite3_exec(kv->db, sql, 0, 0, 0);
-        sqlite3_free(sql);
-        v = live_find(kv->db, tbl);
-    }
-    if (!v) {
-        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: no hnsw_index table named '%s'", tbl ? tbl : "");
-        return SQLITE_ERROR;
-    }
-    if (flush_pending(v) != SQLITE_OK) {
-        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
-        return SQLITE_ERROR;
-    }
-    const int n = mn_hnsw_slot_count(v->index);
-    if (n <= 0 || k < 1 || k > 128) { /* an empty table answers nothing; a k out of range is the library's error to word */
-        if (mn_hnsw_knn_graph(v->index, k, r, 0, 0, 0) != 0) {
-            kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", mn_last_error());
-            return SQLITE_ERROR;
-        }
-        return SQLITE_OK;
-    }
-    c->src = (int64_t *)malloc((size_t)n * sizeof(int64_t));
-    c->ids = (int64_t *)malloc((size_t)n * k * sizeof(int64_t));
-    c->dists = (float *)malloc((size_t)n * k * sizeof(float));
-    c->counts = (int *)malloc((size_t)n * sizeof(int));
-    int *scratch = (int *)malloc((size_t)n * 2 * sizeof(int)); /* levels and deleted flags: not needed, counts say which slots live */
-    if (!c->src || !c->ids || !c->dists || !c->counts || !scratch) {
-        free(scratch);
-        return SQLITE_NOMEM;
-    }
-    int rc = mn_hnsw_export_nodes(v->index, c->src, scratch, scratch + n);
-    free(scratch);
-    if (rc == 0)
-        rc = mn_hnsw_knn_graph(v->index, k, r, c->ids, c->dists, c->counts);
-    if (rc != 0) {
-        kv->base.zErrMsg = sqlite3_mprintf("hnsw_knn_graph: %s", mn_last_error());
-        return SQLITE_ERROR;
-    }
-    c->n = n;
-    c->k = k;
-    k_skip_empty(c);
-    return SQLITE_OK;
-}
-static int k_next(sqlite3_vtab_cursor *cur) {
-    KnnCur *c = (KnnCur *)cur;
-    c->ri++;
-    k_skip_empty(c);
-    return SQLITE_OK;
-}
-static int k_eof(sqlite3_vtab_cursor *cur) {
-    KnnCur *c = (KnnCur *)cur;
-    return c->si >= c->n;
-}
-static int k_column(sqlite3_vtab_cursor *cur, sqlite3_context *ctx, int col) {
-    KnnCur *c = (KnnCur *)cur;
-    size_t at = (size_t)c->si * c->k + c->ri;
-    switch (col) {
-    case KC_SRC: sqlite3_result_int64(ctx, c->src[c->si]); break;
-    case KC_DST: sqlite3_result_int64(ctx, c->ids[at]); break;
-    case KC_DIST: sqlite3_result_double(ctx, (double)c->dists[at]); break;
-    case KC_RANK: sqlite3_result_int(ctx, c->ri); break;
-    default: sqlite3_result_null(ctx); break;
-    }
-    return SQLITE_OK;
-}
-static int k_rowid(sqlite3_vtab_cursor *cur, sqlite3_int64 *out) {
-    KnnCur *c = (KnnCur *)cur;
-    *out = (sqlite3_int64)c->si * c->k + c->ri;
-    return SQLITE_OK;
-}
-static sqlite3_module knn_module = {
-    .iVersion = 0,
-    .xCreate = 0,
-    .xConnect = k_connect,
-    .xBestIndex = k_best_index,
-    .xDisconnect = k_disconnect,
-    .xDestroy = k_disconnect,
-    .xOpen = k_open,
-    .xClose = k_close,
-    .xFilter = k_filter,
-    .xNext = k_next,
-    .xEof = k_eof,
-    .xColumn = k_column,
-    .xRowid = k_rowid,
-};
-
 /* node2vec_train's output step (src/node2vec.c:540-583: INSERT every embedding into the output table) when that table is a
  * live hnsw_index of this connection in fast mode and still empty: the embeddings are trained, normalised and built into the
  * index without leaving HBM (mn_node2vec_train_into) — no per-row INSERT, no second upload — and the shadow tables are written
@@ -1490,9 +1094,7 @@ int mn_vtab_hnsw_fill_from_n2v(sqlite3 *db, const char *table, int n, const int 
     if (!v || v->mode != MODE_FAST || v->dim != prm->dim || v->n_pend != 0 || (e && !strcmp(e, "0")))
         return 0;
     sqlite3_stmt *st = 0;
-    char *sql = sqlite3_mprintf("SELECT count(*) FROM \"%w_nodes\"", v->name);
-    int rc = sqlite3_prepare_v2(db, sql, -1, &st, 0);
-    sqlite3_free(sql);
+    int rc = mn_sql_prepare_owned(db, sqlite3_mprintf("SELECT count(*) FROM \"%w_nodes\"", v->name), &st);
     if (rc != SQLITE_OK)
         return 0;
     const int have = sqlite3_step(st) == SQLITE_ROW ? sqlite3_column_int(st, 0) : 1;
@@ -1526,36 +1128,35 @@ int mn_vtab_hnsw_fill_from_n2v(sqlite3 *db, const char *table, int n, const int 
     return 1;
 }
 
-/* muninn_extract_er (mn_er_sql.c): the device index behind a live hnsw_index table of this connection, its queued rows applied
- * first — what hnsw_knn_graph does before it asks.  NULL + *err (sqlite3_mprintf) when there is no such table or the rows fail. */
-mn_index *mn_vtab_hnsw_index_of(sqlite3 *db, const char *table, char **err) {
-    VtabHnsw *v = live_find(db, table);
-    if (!v) { /* not connected yet on this connection: touching the table connects it */
-        char *sql = sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", table);
-        sqlite3_exec(db, sql, 0, 0, 0);
-        sqlite3_free(sql);
+/* mn_vtab_hnsw.h: what hnsw_search_batch, hnsw_search_exact, hnsw_knn_graph and muninn_extract_er do before they ask the index */
+mn_index *mn_vtab_hnsw_index_of(sqlite3 *db, const char *table, int *dim, char **err) {
+    VtabHnsw *v = table ? live_find(db, table) : 0;
+    if (!v && table) { /* not connected yet on this connection: touching the table connects it */
+        mn_sql_exec_owned(db, sqlite3_mprintf("SELECT rowid FROM \"%w\" WHERE rowid = -1", table));
         v = live_find(db, table);
     }
     if (!v) {
-        *err = sqlite3_mprintf("no hnsw_index table named '%s'", table);
+        *err = sqlite3_mprintf("no hnsw_index table named '%s'", table ? table : "");
         return 0;
     }
     if (flush_pending(v) != SQLITE_OK) {
         *err = sqlite3_mprintf("%s", v->base.zErrMsg ? v->base.zErrMsg : "pending inserts failed");
         return 0;
     }
+    if (dim)
+        *dim = v->dim;
     return v->index;
 }
+
+/* weak, as muninn_ext.c holds its subsystems: a link that leaves mn_hnsw_tvf.c out (the table alone next to other sources)
+ * still loads, and passes the three functions over */
+int mn_register_hnsw_tvfs(sqlite3 *db) __attribute__((weak));
 
 int mn_register_hnsw_module(sqlite3 *db) {
     int rc = sqlite3_create_module(db, "hnsw_index", &hnsw_module, 0); /* src/hnsw_vtab.c:805-807 */
     if (rc == SQLITE_OK)
         rc = sqlite3_create_module(db, "hnsw0", &hnsw_module, 0); /* alias named by BASELINE.json */
-    if (rc == SQLITE_OK)
-        rc = sqlite3_create_module(db, "hnsw_search_batch", &batch_module, 0); /* additive batch surface */
-    if (rc == SQLITE_OK)
-        rc = sqlite3_create_module(db, "hnsw_search_exact", &batch_module, (void *)&batch_module); /* non-NULL aux: the exact flavour */
-    if (rc == SQLITE_OK)
-        rc = sqlite3_create_module(db, "hnsw_knn_graph", &knn_module, 0); /* additive: the self-join of the exact search */
+    if (rc == SQLITE_OK && mn_register_hnsw_tvfs)
+        rc = mn_register_hnsw_tvfs(db); /* additive: the batch surface, its exact counterpart and that one's self-join */
     return rc;
 }

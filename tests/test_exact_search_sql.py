@@ -1,4 +1,4 @@
-"""hnsw_search_exact, the SQL face of the exact search (ext/mn_vtab_hnsw.c), and the three C-ABI symbols behind it.
+"""hnsw_search_exact, the SQL face of the exact search (ext/mn_hnsw_tvf.c), and the three C-ABI symbols behind it.
 The tests without the gpu mark run where no device exists: registration, schema, an error raised before any device call,
 and the exported symbols."""
 import os
@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from util import gauss, same_bits
+from util import gauss, ranks_within, same_bits, small_hnsw_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXT_DIR = os.path.join(ROOT, "sqlite-muninn_amd", "ext")
@@ -51,6 +51,35 @@ def test_unknown_table_fails_before_any_device_call(cpu_conn):
     assert str(ei.value) == "hnsw_search_exact: no hnsw_index table named 'nope'"
     # without its three arguments the function has nothing to answer
     assert cpu_conn.execute("SELECT * FROM hnsw_search_exact").fetchall() == []
+
+
+def test_schema_of_hnsw_search_batch(cpu_conn):
+    cols = cpu_conn.execute("SELECT name, type, hidden FROM pragma_table_xinfo('hnsw_search_batch')").fetchall()
+    assert cols == [("query_idx", "INTEGER", 0), ("id", "INTEGER", 0), ("distance", "REAL", 0), ("tbl", "TEXT", 1),
+                    ("queries", "BLOB", 1), ("k", "INTEGER", 1), ("ef_search", "INTEGER", 1)]
+
+
+@pytest.mark.parametrize("fn", ["hnsw_search_batch", "hnsw_search_exact"])
+def test_a_missing_required_argument_answers_nothing(cpu_conn, fn):
+    """Not an error, even when tbl names no table: the function is never asked."""
+    assert cpu_conn.execute(f"SELECT * FROM {fn} WHERE tbl='nope'").fetchall() == []
+    assert cpu_conn.execute(f"SELECT * FROM {fn} WHERE tbl='nope' AND k=3").fetchall() == []
+
+
+@pytest.mark.parametrize("fn", ["hnsw_search_batch", "hnsw_search_exact"])
+def test_arguments_are_bound_by_column_not_by_their_place_in_the_text(cpu_conn, fn):
+    q = np.zeros(4, np.float32).tobytes()
+    with pytest.raises(sqlite3.OperationalError) as ei:
+        cpu_conn.execute(f"SELECT * FROM {fn} WHERE k=3 AND queries=? AND tbl='nope'", (q,)).fetchall()
+    assert str(ei.value) == f"{fn}: no hnsw_index table named 'nope'"
+
+
+@pytest.mark.parametrize("fn", ["hnsw_search_batch", "hnsw_search_exact"])
+def test_a_null_table_name_is_reported_as_the_empty_name(cpu_conn, fn):
+    q = np.zeros(4, np.float32).tobytes()
+    with pytest.raises(sqlite3.OperationalError) as ei:
+        cpu_conn.execute(f"SELECT * FROM {fn} WHERE tbl=? AND queries=? AND k=3", (None, q)).fetchall()
+    assert str(ei.value) == f"{fn}: no hnsw_index table named ''"
 
 
 def test_library_exports_the_entry_points(mn):
@@ -131,3 +160,23 @@ def test_rows_queued_in_the_open_transaction_are_found(mn, gpu, monkeypatch):
     assert rows == [(0, 6, 0.0), (1, 40, 0.0)]
     c.execute("COMMIT")
     c.close()
+
+
+@pytest.mark.gpu
+def test_rows_are_numbered_by_query_and_rank(cpu_conn, gpu):
+    """rowid = query_idx * k + rank within the query, for both functions; a query with fewer than k rows leaves a gap in the
+    numbering, a query with none is skipped, and an answer of empty groups only is no rows."""
+    c = cpu_conn
+    small_hnsw_table(c, "sv")
+    Q, k = gauss(5, 8, 102).tobytes(), 3
+    for fn in ("hnsw_search_batch", "hnsw_search_exact"):
+        rows = c.execute(f"SELECT rowid, query_idx, id FROM {fn} WHERE tbl='sv' AND queries=? AND k=?", (Q, k)).fetchall()
+        assert [r[1] for r in rows] == [qi for qi in range(5) for _ in range(k)], fn
+        assert [r[0] for r in rows] == [r[1] * k + rank for r, rank in zip(rows, ranks_within(r[1] for r in rows))], fn
+        assert not {7, 23} & {r[2] for r in rows}, fn
+    sql = "SELECT rowid, query_idx, id FROM hnsw_search_exact WHERE tbl='sv' AND queries=? AND k=? AND allow=?"
+    rows = c.execute(sql, (Q, k, np.array([3, 30], np.int64).tobytes())).fetchall()
+    assert [r[1] for r in rows] == [qi for qi in range(5) for _ in range(2)]  # two rows a query: fewer than k
+    assert [r[0] for r in rows] == [0, 1, 3, 4, 6, 7, 9, 10, 12, 13]
+    assert all({r[2] for r in rows if r[1] == qi} == {3, 30} for qi in range(5))
+    assert c.execute(sql, (Q, k, np.array([7], np.int64).tobytes())).fetchall() == []  # a deleted row: every group is empty

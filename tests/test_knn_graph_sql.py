@@ -1,4 +1,4 @@
-"""hnsw_knn_graph, the SQL face of the exact k-NN graph (ext/mn_vtab_hnsw.c), and the two C-ABI symbols behind it.
+"""hnsw_knn_graph, the SQL face of the exact k-NN graph (ext/mn_hnsw_tvf.c), and the two C-ABI symbols behind it.
 The tests without the gpu mark run where no device exists: registration, schema, an error raised before any device call,
 and the exported symbols."""
 import os
@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from util import gauss, same_bits
+from util import gauss, ranks_within, same_bits, small_hnsw_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXT_DIR = os.path.join(ROOT, "sqlite-muninn_amd", "ext")
@@ -58,6 +58,18 @@ def test_no_rows_without_arguments(cpu_conn):
     assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph").fetchall() == []
     assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE k=5").fetchall() == []
     assert cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE tbl='nope'").fetchall() == []
+
+
+def test_arguments_are_bound_by_column_not_by_their_place_in_the_text(cpu_conn):
+    with pytest.raises(sqlite3.OperationalError) as ei:
+        cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE max_distance=0.5 AND k=5 AND tbl='nope'").fetchall()
+    assert str(ei.value) == "hnsw_knn_graph: no hnsw_index table named 'nope'"
+
+
+def test_a_null_table_name_is_reported_as_the_empty_name(cpu_conn):
+    with pytest.raises(sqlite3.OperationalError) as ei:
+        cpu_conn.execute("SELECT * FROM hnsw_knn_graph WHERE tbl=? AND k=5", (None,)).fetchall()
+    assert str(ei.value) == "hnsw_knn_graph: no hnsw_index table named ''"
 
 
 def test_library_exports_the_entry_points(mn):
@@ -158,3 +170,35 @@ def test_knn_graph_into_leiden(mn, gpu, orc):
         members.setdefault(com, set()).add(int(blob[int(node) - 1]))
     assert len(members) >= 2 and all(len(b) == 1 for b in members.values()), members
     c.close()
+
+
+@pytest.mark.gpu
+def test_rows_are_numbered_by_slot_and_rank(cpu_conn, gpu):
+    """rowid = slot * k + rank, slot the 0-based insertion index of src (here rowid - 1) and rank restarting at 0 for every src:
+    a max_distance that cuts lists short or empty leaves gaps in the numbering, and a deleted row has no list at all."""
+    c = cpu_conn
+    small_hnsw_table(c, "kv")
+    k, sql = 3, "SELECT rowid, src, dst, distance, rank FROM hnsw_knn_graph WHERE tbl='kv' AND k=?"
+    full = c.execute(sql, (k,)).fetchall()
+    live = [i for i in range(1, 41) if i not in (7, 23)]
+    assert [r[1] for r in full] == [s for s in live for _ in range(k)]
+    r = float(np.float32(np.median(np.array([row[3] for row in full], np.float32))))
+    rows = c.execute(sql + " AND max_distance=?", (k, r)).fetchall()
+    assert rows == [row for row in full if np.float32(row[3]) <= np.float32(r)]
+    per_src = [sum(1 for row in rows if row[1] == s) for s in live]
+    assert 0 < len(rows) < len(full) and min(per_src) < k  # some lists are short or empty
+    assert [row[4] for row in rows] == ranks_within(row[1] for row in rows)
+    assert [row[0] for row in rows] == [(row[1] - 1) * k + row[4] for row in rows]
+    assert not {7, 23} & ({row[1] for row in rows} | {row[2] for row in rows})
+
+
+@pytest.mark.gpu
+def test_k_out_of_range_is_the_librarys_error_and_an_empty_table_answers_nothing(cpu_conn, gpu):
+    c = cpu_conn
+    small_hnsw_table(c, "kv")
+    for bad in (0, 129):
+        with pytest.raises(sqlite3.OperationalError) as ei:
+            c.execute("SELECT * FROM hnsw_knn_graph WHERE tbl='kv' AND k=?", (bad,)).fetchall()
+        assert str(ei.value) == f"hnsw_knn_graph: mn_hnsw_knn_graph: k must be 1..128 (got {bad})"
+    c.execute("CREATE VIRTUAL TABLE et USING hnsw_index(dimensions=8, metric='l2', m=4)")
+    assert c.execute("SELECT * FROM hnsw_knn_graph WHERE tbl='et' AND k=3").fetchall() == []

@@ -347,6 +347,20 @@ def test_hnsw_search_batch_tvf_equals_per_query_results(conn, gpu):
 
 
 @gpu_mark
+def test_hnsw_search_batch_default_ef_search_and_k_zero(conn, gpu):
+    """Without ef_search the rows are those of ef_search = 2 * k; k = 0 is refused in the words of the queries check."""
+    from util import gauss, small_hnsw_table
+    small_hnsw_table(conn, "sv")
+    Q, k = gauss(5, 8, 102).tobytes(), 3
+    sql = "SELECT rowid, query_idx, id, distance FROM hnsw_search_batch WHERE tbl='sv' AND queries=? AND k=?"
+    rows = conn.execute(sql, (Q, k)).fetchall()
+    assert len(rows) == 5 * k and rows == conn.execute(sql + " AND ef_search=?", (Q, k, 2 * k)).fetchall()
+    with pytest.raises(sqlite3.OperationalError) as ei:
+        conn.execute(sql, (Q, 0)).fetchall()
+    assert str(ei.value) == "hnsw_search_batch: queries must be a multiple of 32 bytes (8-dim f32), got 160"
+
+
+@gpu_mark
 def test_graph_leiden_sql_fast_mode_matches_oracle_schedule(conn, gpu, monkeypatch):
     """MUNINN_GRAPH_MODE=fast → MN_LEIDEN_BATCHED's default schedule (whole-graph synchronous sweeps, pick-less every 3rd);
     must equal the CPU restatement of it (oracle batch -3)."""

@@ -14,6 +14,29 @@ def gauss(n, d, seed):
     return np.random.default_rng(seed).standard_normal((n, d), dtype=np.float32)
 
 
+def small_hnsw_table(c, name):
+    """The smallest table on which a grouped cursor can go wrong: 40 rows of dim 8 under rowids 1..40 (slot = rowid - 1),
+    l2, m = 4, then rowids 7 and 23 deleted.  Returns the vectors."""
+    X = gauss(40, 8, 101)
+    c.execute(f"CREATE VIRTUAL TABLE {name} USING hnsw_index(dimensions=8, metric='l2', m=4)")
+    with c:
+        for i in range(40):
+            c.execute(f"INSERT INTO {name} (rowid, vector) VALUES (?, ?)", (i + 1, X[i].tobytes()))
+        for gone in (7, 23):
+            c.execute(f"DELETE FROM {name} WHERE rowid = ?", (gone,))
+    return X
+
+
+def ranks_within(groups):
+    """0, 1, 2, ... restarting whenever the group changes: the rank of every row within its group, rows as they came."""
+    out, last, r = [], object(), 0
+    for g in groups:
+        r = r + 1 if g == last else 0
+        last = g
+        out.append(r)
+    return out
+
+
 def recall_at_k(found, truth):
     hit = 0
     for f, t in zip(found, truth):
